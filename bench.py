@@ -7,6 +7,13 @@ One step = one pass of the hot path over the resident synthetic cluster:
 Inputs are resident in HBM before the timed region; value = nodes x specs of the
 whole job / step time (max over ranks).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints one JSON line: the headline figure, ms_per_step, and a checksum of the
+totals.  --dump-outputs DIR also writes the last timed step's outputs as DIR/<name>.npy.
+--full adds everything measured or checked beside the step (per-kernel events and
+rooflines, cold-cache and dense-layout steps, the upload, the CPU baseline, the keyed /
+pod / parse legs, the multi-rank exchange's post-check) to the same line.
+
 Default workload = BASELINE config C4 (1M nodes, ~20M pods / ~40M containers, 4096
 specs), which fits one MI355X.  --gpus N: one process per GPU; the SAME 1M-node
 cluster is split into N contiguous node ranges (strong scaling, BASELINE configs[3]:
@@ -86,6 +93,16 @@ def parse():
     ap.add_argument("--chunks", type=int, default=1,
                     help="node chunks of the pipelined step (reduce of chunk k overlaps the fit "
                          "of chunk k-1); 1 = reduce, then fit")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the "
+                         "headline figure: per-kernel events and rooflines, cold-cache and "
+                         "dense-layout steps, the upload, the CPU baseline, the keyed / pod / "
+                         "parse legs, the exchange's post-check (each still has its --no-* "
+                         "switch); without it a run sets up, warms up, times --steps steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (rank 0: "
+                         "used_cpu, used_mem, totals, spec_err) as DIR/<name>.npy in float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--clamp-in-fit", type=int, default=-1, choices=[-1, 0, 1],
                     help="pod-slot clamp inside the fit: -1 by shard size (default), 0 never "
@@ -109,8 +126,8 @@ def parse():
                     help="diagnostic: run only rank 0's node shard of a world of this size "
                          "(no all-reduce) to estimate per-rank step time at N GPUs")
     ap.add_argument("--kernel-events", default="after", choices=["timed", "after"],
-                    help="per-kernel HIP events inside the timed steps (timed) or in as many "
-                         "extra steps after them (after)")
+                    help="--full: per-kernel HIP events inside the timed steps (timed) or in as "
+                         "many extra steps after them (after)")
     ap.add_argument("--graph", type=int, default=0, choices=[0, 1],
                     help="1: the timed steps replay one step captured into a HIP graph "
                          "(torch.cuda.CUDAGraph on the bench stream; every kernel still runs "
@@ -124,7 +141,30 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: start the ranks, exchange one gloo "
                          "all-reduce, print the rank count (no measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the device arrays a caller of the timed path receives, as
+    <path>/<name>.npy in float64 (the sums stay below 2^53 for every config's cluster, so
+    the conversion is exact).  Arrays that together exceed DUMP_BUDGET_BYTES are each cut
+    to an equal share of it: a fixed sample of their elements (seeded by the array's
+    position and length, in index order), the same from run to run and from build to build."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.cpu().numpy() for k, v in arrays.items()}
+    share = DUMP_BUDGET_BYTES // 8 // len(host)
+    fits = sum(a.size for a in host.values()) * 8 <= DUMP_BUDGET_BYTES
+    for i, (name, a) in enumerate(host.items()):
+        if not fits and a.size > share:
+            rng = np.random.Generator(np.random.PCG64([20261020, i, a.size]))
+            a = a[np.sort(rng.choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 def relaunch(args) -> int:
@@ -423,7 +463,7 @@ def main():
         # per-launch kernel durations from HIP events the library records on the stream
         # each kernel runs on: over exactly the timed steps (--kernel-events timed), or
         # over as many extra steps right after them (after: the timed region has no events)
-        eng.profile_enable(args.kernel_events == "timed" and graph is None)
+        eng.profile_enable(args.full and args.kernel_events == "timed" and graph is None)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -434,15 +474,16 @@ def main():
         if world > 1:
             dist.barrier()
         t_end = time.perf_counter()
-        if args.kernel_events == "after" or graph is not None:
+        if args.dump_outputs and rank == 0:
+            # what the last timed step left in the caller's arrays, before any later leg
+            # runs the step again
+            dump_outputs(args.dump_outputs, {"used_cpu": used_cpu, "used_mem": used_mem,
+                                             "totals": totals, "spec_err": err})
+        if args.full and (args.kernel_events == "after" or graph is not None):
             eng.profile_enable(True)
             for _ in range(args.steps):
                 step(prof=True)
             torch.cuda.synchronize()
-    red_ms_tot, red_launches, fit_ms_tot, fit_launches = eng.profile_read()
-    eng.profile_enable(False)
-    cold = None if args.no_cold else cold_leg(eng, step, stream, dev, args.steps, dist, world)
-    ar_ms = (sum(a.elapsed_time(b) for a, b in ar_events) / len(ar_events)) if ar_events else None
     elapsed = t_end - t_start
     own_ms_step = elapsed / args.steps * 1e3  # this rank's own timed steps
     if world > 1:
@@ -450,13 +491,81 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_step = elapsed / args.steps * 1e3
+    value = n_total * S / (elapsed / args.steps)
+    if args.emulate_world > 1:  # per-rank rate x world (no all-reduce): an upper bound
+        value = n * S * args.emulate_world / (elapsed / args.steps)
+    # the headline figure and what describes the run: every line carries these
+    head = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "int64",
+        "full": args.full,
+        "data": "synthetic (seeded SURVEY §8d generator, kubernetesclustercapacity_amd/synth.py)",
+        "config": {
+            "workload": f"{args.config}: {n_total} nodes x {pods_total} pods x {S} specs; "
+                        "reduce + fit prepare + fit + finalize"
+                        + (" + RCCL all-reduce" if world > 1 else ""),
+            "nodes": n_total, "pods": pods_total, "containers_rank0": C, "nodes_rank0": n,
+            "pods_rank0": int(cl.pod_count.sum()),
+            "pods_per_node": ("Zipf(s=1.2) capped at 2 x allocatable pods (SURVEY §8d); `pods` "
+                              "is its expected total" if cl.meta["skew"] == "zipf" else
+                              f"{cl.meta['skew']}, mean {pods_total / max(n_total, 1):g}"),
+            "specs": S, "parallelism": f"node-sharded x{world}",
+        },
+        "world": {
+            "ranks": world, "process_group_size": dist.get_world_size() if world > 1 else 1,
+            "backend": args.dist_backend if world > 1 else None,
+            "exchange": (("one-shot push over xGMI peer memory + finalize, one kernel "
+                          "(kcc_exchange_finalize_async, kernel stream)" if exchange == "p2p" else
+                          "libkcc RCCL (kcc_allreduce_partial_async, kernel stream)"
+                          if exchange == "kcc" else f"torch.distributed.all_reduce ({args.dist_backend})")
+                         if world > 1 else None),
+            "exchange_note": exchange_note,
+            "visible_gpus": n_dev,
+        },
+        "gen_seconds": gen_s,
+    }
+
+    def add_results(out):
+        # what the timed steps left behind: the reduce's fault word, and an
+        # order-independent fingerprint of the per-spec totals, identical for every N
+        out["reduce_lookback_faults"] = eng.reduce_faults()  # 0 on a healthy device (else sums are wrong)
+        tot_np = totals.cpu().numpy().view(np.uint64)
+        out["totals_checksum"] = int(((tot_np * np.uint64(0x9E3779B97F4A7C15)) ^ (tot_np >> np.uint64(29)))
+                                     .sum(dtype=np.uint64))
+        out["spec_errors"] = int(err.cpu().numpy().sum())
+        if verified is not None:
+            out["exchange_precheck"] = verified
+        if args.lib:
+            out["library"] = args.lib  # a diagnostic variant build, not the release library
+        if args.emulate_world > 1:
+            out["emulated_world"] = args.emulate_world
+
+    if not args.full:  # a plain run ends here: the line for the timed steps, nothing beside them
+        add_results(head)
+        eng.close()
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    red_ms_tot, red_launches, fit_ms_tot, fit_launches = eng.profile_read()
+    eng.profile_enable(False)
+    cold = None if args.no_cold else cold_leg(eng, step, stream, dev, args.steps, dist, world)
+    ar_ms = (sum(a.elapsed_time(b) for a, b in ar_events) / len(ar_events)) if ar_events else None
     chunks = fit_launches // args.steps
     red_ms = red_ms_tot / max(red_launches, 1)   # per launch
     fit_ms = fit_ms_tot / max(fit_launches, 1)
     slow_pairs, pairs = eng.fit_slow_pairs()
-    value = n_total * S / (elapsed / args.steps)
-    if args.emulate_world > 1:  # per-rank rate x world (no all-reduce): an upper bound
-        value = n * S * args.emulate_world / (elapsed / args.steps)
 
     # the fit's node stream: the rows that can add to its fast sum (free CPU, free memory,
     # pods > 0; every other row adds exactly 0 there), compacted by node_prep
@@ -489,40 +598,7 @@ def main():
         fit_traffic = red_traffic = tsrc = None
 
     out = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "evals/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "int64",
-        "data": "synthetic (seeded SURVEY §8d generator, kubernetesclustercapacity_amd/synth.py)",
-        "config": {
-            "workload": f"{args.config}: {n_total} nodes x {pods_total} pods x {S} specs; "
-                        "reduce + fit prepare + fit + finalize"
-                        + (" + RCCL all-reduce" if world > 1 else ""),
-            "nodes": n_total, "pods": pods_total, "containers_rank0": C, "nodes_rank0": n,
-            "pods_rank0": int(cl.pod_count.sum()),
-            "pods_per_node": ("Zipf(s=1.2) capped at 2 x allocatable pods (SURVEY §8d); `pods` "
-                              "is its expected total" if cl.meta["skew"] == "zipf" else
-                              f"{cl.meta['skew']}, mean {pods_total / max(n_total, 1):g}"),
-            "specs": S, "parallelism": f"node-sharded x{world}",
-        },
-        "world": {
-            "ranks": world, "process_group_size": dist.get_world_size() if world > 1 else 1,
-            "backend": args.dist_backend if world > 1 else None,
-            "exchange": (("one-shot push over xGMI peer memory + finalize, one kernel "
-                          "(kcc_exchange_finalize_async, kernel stream)" if exchange == "p2p" else
-                          "libkcc RCCL (kcc_allreduce_partial_async, kernel stream)"
-                          if exchange == "kcc" else f"torch.distributed.all_reduce ({args.dist_backend})")
-                         if world > 1 else None),
-            "exchange_note": exchange_note,
-            "visible_gpus": n_dev,
-        },
+        **head,
         # the dominant kernel of the step (longest per step): its HBM roofline
         "roofline": None,
         "roofline_fit": {
@@ -577,7 +653,6 @@ def main():
                              + ("; the timed steps replay one captured HIP graph"
                                 if graph is not None else "")},
         "fast_path_fraction": 1.0 - (slow_pairs / pairs if pairs else 0.0),
-        "gen_seconds": gen_s,
     }
     if np_fused:
         lb = red_bytes + np_bytes
@@ -606,26 +681,13 @@ def main():
                                note="dominant kernel of the step; VALU issue-bound (no MFMA or HBM "
                                     "bound applies: 3 VALU per node and 64-spec wave); the HBM "
                                     "view: roofline_fit")
-    if args.emulate_world > 1:
-        out["emulated_world"] = args.emulate_world
     # every rank's own numbers (N > 1: who is slowest, and what the exchange costs)
     out["ranks"] = rank_stats(dist, world, {"step_ms": own_ms_step, "reduce_ms": red_ms,
                                             "fit_ms": fit_ms, "allreduce_ms": ar_ms,
                                             "reduce_frac": red_gbs / HBM_PEAK_GBS},
                               device=dev if args.dist_backend == "nccl" else None)
     out["allreduce_ms"] = out["ranks"]["allreduce_ms"]
-    faults = eng.reduce_faults()
-    out["reduce_lookback_faults"] = faults  # 0 on a healthy device (else sums are wrong)
-
-    # order-independent fingerprint of the per-spec totals: identical for every N
-    tot_np = totals.cpu().numpy().view(np.uint64)
-    out["totals_checksum"] = int(((tot_np * np.uint64(0x9E3779B97F4A7C15)) ^ (tot_np >> np.uint64(29)))
-                                 .sum(dtype=np.uint64))
-    out["spec_errors"] = int(err.cpu().numpy().sum())
-    if verified is not None:
-        out["exchange_precheck"] = verified
-    if args.lib:
-        out["library"] = args.lib  # a diagnostic variant build, not the release library
+    add_results(out)
     if world > 1 and exchange == "p2p":
         # again after the timed steps: the p2p exchange against the process group's
         # all-reduce of the same partials + the library's finalize (every rank), and the

@@ -15,7 +15,7 @@ for round in base $VAR base2 ${VAR}2; do
                  *) cp variants/libkcc_$VAR.so kubernetesclustercapacity_amd/libkcc.so ;; esac
   for W in "$@"; do
     OUT=gpurun_out/abl_${TAG}_${round}_w$W.json
-    timeout -k 10 200 python3 -u bench.py --config C4 --scaling strong --emulate-world $W \
+    timeout -k 10 200 python3 -u bench.py --full --config C4 --scaling strong --emulate-world $W \
       --no-cpu-baseline --no-keyed --no-pods --no-parse --no-dense --steps 100 --warmup 10 \
       > $OUT 2> ${OUT%.json}.err || exit $?
     echo "$round W=$W $(grep -o '"ms_per_step": [0-9.]*' $OUT) fit $(python3 -c "import json;print(round(json.load(open('$OUT'))['pipeline']['fit_ms_per_step']*1e3,2))")"

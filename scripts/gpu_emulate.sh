@@ -9,7 +9,7 @@ TAG=$1; CFG=$2; shift 2
 mkdir -p gpurun_out
 for W in "$@"; do
   OUT=gpurun_out/emu_${TAG}_${CFG}_w$W.json
-  timeout -k 10 200 python3 -u bench.py --config $CFG --scaling strong --emulate-world $W \
+  timeout -k 10 200 python3 -u bench.py --full --config $CFG --scaling strong --emulate-world $W \
     --no-cpu-baseline --no-keyed --no-pods --no-parse --no-dense --steps 50 --warmup 5 ${EXTRA:-} \
     > $OUT 2> ${OUT%.json}.err || exit $?
   echo "== $CFG W=$W: $(grep -o '"ms_per_step": [0-9.]*' $OUT)"

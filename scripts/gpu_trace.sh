@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/trace_${1:-x}
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run \
-  -- python3 bench.py --no-cpu-baseline --steps 10 --warmup 2 "${@:2}" > $OUT/bench.log 2>&1 || exit $?
+  -- python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 2 "${@:2}" > $OUT/bench.log 2>&1 || exit $?
 f=$(find $OUT -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 TAG=$1; CFG=$2; W=$3
 OUT=gpurun_out/pmcshard_${TAG}_${CFG}_w$W
 mkdir -p $OUT
-B="python3 bench.py --config $CFG --scaling strong --emulate-world $W --no-cpu-baseline --no-keyed --no-pods --no-parse --no-dense"
+B="python3 bench.py --full --config $CFG --scaling strong --emulate-world $W --no-cpu-baseline --no-keyed --no-pods --no-parse --no-dense"
 i=0
 for pmc in FETCH_SIZE WRITE_SIZE; do
   i=$((i+1))

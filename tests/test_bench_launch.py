@@ -54,3 +54,36 @@ def test_single_rank_dry_run():
                        timeout=120, env=_env())
     assert r.returncode == 0, r.stderr[-2000:]
     assert _last_json(r.stdout)["n_gpus"] == 1
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files; arrays over the budget are cut to a fixed sample (the
+    same indices on every run, in index order), small ones are written whole."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    big = torch.arange(10_000, dtype=torch.int64) * 3
+    small = torch.tensor([5, -1, 7], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "whole"), {"big": big, "small": small})
+    w = np.load(tmp_path / "whole" / "big.npy")
+    assert w.dtype == np.float64 and np.array_equal(w, big.numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "small.npy"), [5.0, -1.0, 7.0])
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 8 * 1000)  # 1000 elements per array
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.size == 1000 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.all(np.isin(a, big.numpy()))
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), [5.0, -1.0, 7.0])
+    total = sum(np.load(tmp_path / "a" / f).nbytes for f in ("big.npy", "small.npy"))
+    assert total <= bench.DUMP_BUDGET_BYTES
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0", "--dry-run"], capture_output=True,
+                       text=True, timeout=120, env=_env())
+    assert r.returncode == 2 and "--steps" in r.stderr

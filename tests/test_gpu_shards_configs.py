@@ -310,7 +310,7 @@ def _bench(*extra):
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR",
                         "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C3",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-keyed",
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-keyed",
                         "--no-pods", "--no-parse", *extra], capture_output=True, text=True,
                        timeout=100, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -343,6 +343,43 @@ def test_bench_exchange_fallback_drill():
     assert pre["verified_before_timing"] and pre["exchanges_tried"] == ["p2p", "torch"]
     assert "failed its pre-timing check" in two["world"]["exchange_note"]
     assert two["totals_checksum"] == one["totals_checksum"]
+
+
+def test_bench_plain_run_line_and_dump(tmp_path):
+    """A plain run (no --full): the headline line only, --steps timed steps, and with
+    --dump-outputs the last step's outputs in float64: the line's checksum is theirs, the
+    totals and flags are the C oracle's, the per-node sums the CSR reduce's."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR",
+                        "MASTER_PORT")}
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config",
+                        "C3", "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=100, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "evals/s" and line["higher_is_better"] and line["dtype"] == "int64"
+    assert line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(100_000 * 256 / (line["ms_per_step"] * 1e-3))
+    assert line["reduce_lookback_faults"] == 0
+    for k in ("roofline", "cold", "dense_layout", "cpu_baseline", "keyed", "pods", "parse", "h2d"):
+        assert k not in line
+    out = {f: np.load(d / f"{f}.npy") for f in ("used_cpu", "used_mem", "totals", "spec_err")}
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert out["used_cpu"].shape == out["used_mem"].shape == (100_000,)
+    assert out["totals"].shape == out["spec_err"].shape == (256,)
+    tot = out["totals"].astype(np.int64).view(np.uint64)
+    chk = int(((tot * np.uint64(0x9E3779B97F4A7C15)) ^ (tot >> np.uint64(29))).sum(dtype=np.uint64))
+    assert chk == line["totals_checksum"]
+    assert int(out["spec_err"].sum()) == line["spec_errors"]
+    c = synth.config_cluster("C3", limits=False)
+    ot, oe = oracle_totals(c, *synth.config_specs("C3"))
+    np.testing.assert_array_equal(out["totals"], ot.astype(np.float64))
+    np.testing.assert_array_equal(out["spec_err"], oe.astype(np.float64))
+    np.testing.assert_array_equal(out["used_cpu"], seg_sums(c.node_ptr, c.cpu_req).astype(np.float64))
+    np.testing.assert_array_equal(out["used_mem"],
+                                  seg_sums(c.node_ptr, c.mem_req).view(np.int64).astype(np.float64))
 
 
 # ---- the fit's node stream: compacted (default) == every row (dense) -----------------------

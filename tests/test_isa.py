@@ -23,13 +23,17 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "kubernetesclustercapacity_amd", "csrc", "kcc_kernels.hip")
 
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
+# hipcc from PATH, else where csrc/Makefile takes it from ($(ROCM)/bin/hipcc)
+HIPCC = shutil.which("hipcc") or shutil.which(
+    os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc"))
+
+pytestmark = pytest.mark.skipif(HIPCC is None, reason="hipcc not available")
 
 
 @pytest.fixture(scope="module")
 def asm(tmp_path_factory):
     out = tmp_path_factory.mktemp("isa") / "kcc.s"
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S",
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S",
                     "--cuda-device-only", SRC, "-o", str(out)], check=True,
                    capture_output=True)
     return out.read_text()
@@ -271,7 +275,7 @@ def _src_lines(pattern, within=None):
 
 def _asm_with_lines(tmp_path_factory, *defines):
     out = tmp_path_factory.mktemp("isa_g") / "kcc_g.s"
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S",
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S",
                     "--cuda-device-only", "-gline-tables-only", *defines, SRC, "-o", str(out)],
                    check=True, capture_output=True)
     return out.read_text()
