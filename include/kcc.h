@@ -316,7 +316,9 @@ int kcc_set_fit_dense(kcc_ctx* ctx, int dense);
  * (a dominance count over the specs, one launch of its own; the fit's loop stays at 3 VALU
  * per node and spec wave) or inside the fit (5 VALU, no clamp launch, no clamp tables:
  * cheaper on small shards).  mode -1 (default): inside the fit when node rows x specs <=
- * 1.1e9 and specs <= 4096; 0: never; 1: whenever specs <= 4096 (one node chunk, not dense).
+ * 1.1e9 and specs <= 4096; 0: never; 1: whenever specs <= 4096 (one node chunk, not dense,
+ * at least one node and one container).  A call that does not qualify applies the clamp by
+ * the correction in every mode, and kcc_clamp_in_fit_used reports 0 for it.
  * The totals are the same bit for bit either way. */
 int kcc_set_clamp_in_fit(kcc_ctx* ctx, int mode);
 /* 1 when the last kcc_capacity_partial_async / kcc_capacity_async of the context applied

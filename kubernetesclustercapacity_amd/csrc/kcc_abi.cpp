@@ -451,7 +451,7 @@ int fit_prepare_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, const uint64_t* allo
                                        as<kcc::FitGroup>(dv.fast_b), as<kcc::SlowNode>(dv.slow),
                                        as<int64_t>(dv.slow_list), n_specs, clamp_of(dv),
                                        as<unsigned long long>(dv.counters), 0, 0,
-                                       n_nodes, s, dv.fit_dense, &pa, nullptr));
+                                       n_nodes, s, dv.fit_dense, &pa));
   if (n_nodes == 0) {
     dv.clamp_dirty = false;
     return KCC_OK;
@@ -514,10 +514,6 @@ hipError_t prof_event(Dev& dv, hipEvent_t* ev) {
   // on the stream)
   return hipEventCreateWithFlags(ev, hipEventDisableSystemFence);
 }
-
-#ifndef KCC_NP_IN_REDUCE
-#define KCC_NP_IN_REDUCE 1
-#endif
 
 // Chunk boundaries: node ranges of ~equal node count, multiples of CHUNK_ALIGN (a
 // multiple of FIT_GROUP: the fit's node groups do not straddle two chunks); at least
@@ -605,8 +601,9 @@ int capacity_partial_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, int64_t n_cont,
   // place, fit, clamp_apply
   const bool fuse_place = n_specs > 0;
   const bool fuse_rank = k == 1 && fuse_place && n_nodes > 0 && n_cont > 0;
-  // the clamp in the fit (one node chunk, S <= CLAMP_LDS_SPECS, not dense): no clamp_apply
-  const bool nc = k == 1 && n_specs > 0 && n_specs <= kcc::CLAMP_LDS_SPECS && !dv.fit_dense &&
+  // the clamp in the fit (one node chunk, S <= CLAMP_LDS_SPECS, not dense, at least one node
+  // and one container: the ranks ride in the reduce launch): no clamp_apply
+  const bool nc = fuse_rank && n_specs <= kcc::CLAMP_LDS_SPECS && !dv.fit_dense &&
                   (dv.clamp_in_fit == 1 ||
                    (dv.clamp_in_fit < 0 && kcc::clamp_in_fit_auto(n_nodes, n_specs)));
   int32_t* const fast_cl = nc ? as<int32_t>(dv.fast_cl) : nullptr;
@@ -618,11 +615,10 @@ int capacity_partial_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, int64_t n_cont,
                                     as<uint32_t>(dv.rank_arrive), nc);
   kcc::PlaceArgs pa = place_args(dv, n_specs, spec_cpu, spec_mem, partial);
   pa.no_ranks = nc ? 1 : 0;
-  // the clamp in the fit with the ranks in the reduce launch: spec_place and node_prep's
-  // work ride there too, behind the reduce's workgroups (kcc::NpArgs) — one launch fewer
-  const bool np_fused = KCC_NP_IN_REDUCE && nc && fuse_rank;
+  // spec_place and node prep's row pass ride in the reduce launch too, behind the reduce's
+  // workgroups (kcc::NpArgs): no node_prep launch
   kcc::NpArgs np{};
-  if (np_fused) {
+  if (nc) {
     ra.done_flag = as<uint32_t>(dv.np_sync);
     np.n_place = (int32_t)((n_specs + 255) / 256);
     np.n_rows = (int32_t)((n_nodes + kcc::NP_ROWS_PER_WG - 1) / kcc::NP_ROWS_PER_WG);
@@ -662,7 +658,7 @@ int capacity_partial_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, int64_t n_cont,
                                     used_cpu + lo[c], used_mem + lo[c], nullptr, nullptr,
                                     as<uint64_t>(dv.red_tail),
                                     as<unsigned long long>(dv.faults), rs,
-                                    fuse_rank ? &ra : nullptr, np_fused ? &np : nullptr,
+                                    fuse_rank ? &ra : nullptr, nc ? &np : nullptr,
                                     dv.prof_on ? pp.a : nullptr, dv.prof_on ? pp.b : nullptr));
     if (dv.prof_on) {
       pp.kind = 0;
@@ -678,7 +674,7 @@ int capacity_partial_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, int64_t n_cont,
     const int64_t n = hi[c] - lo[c];
     const bool place_here = fuse_place && c == 0;
     if (n_specs == 0 || (n == 0 && !place_here)) continue;
-    if (!np_fused)  // (else: in the reduce launch)
+    if (!nc)  // (else: in the reduce launch)
     KCC_HIP(ctx, kcc::launch_node_prep(n, alloc_cpu + lo[c], alloc_mem + lo[c], alloc_pods + lo[c],
                                        pod_count + lo[c], used_cpu + lo[c], used_mem + lo[c],
                                        as<kcc::FitGroupA>(dv.fast_a) + lo[c] / kcc::FIT_GROUP,
@@ -687,7 +683,7 @@ int capacity_partial_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, int64_t n_cont,
                                        as<int64_t>(dv.slow_list) + lo[c], n_specs, clamp_of(dv),
                                        as<unsigned long long>(dv.counters),
                                        c, lo[c], n_nodes, s, dv.fit_dense,
-                                       place_here ? &pa : nullptr, fast_cl));
+                                       place_here ? &pa : nullptr));
     if (n == 0) continue;
     ProfPair pp{};
     if (dv.prof_on) {

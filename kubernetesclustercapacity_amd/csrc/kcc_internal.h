@@ -13,7 +13,7 @@
     (defined(KCC_DIAG_RED_NOSTORE) || defined(KCC_DIAG_RED_LOADONLY) ||                  \
      defined(KCC_TIMELINE) || defined(KCC_DIAG_RED_GIVEUP) || defined(KCC_DIAG_P2P_GIVEUP) || \
      defined(KCC_DIAG_INLIB_COMM) || defined(KCC_DIAG_GA_NOATOM) ||                     \
-     defined(KCC_DIAG_NP_NOSYNC) || defined(KCC_DIAG_NP_NOSC1))
+     defined(KCC_DIAG_NP_NOSC1))
 #error "a diagnostic KCC_* knob in a release build: use `make variant` (KCC_VARIANT_BUILD)"
 #endif
 
@@ -311,10 +311,12 @@ struct PlaceArgs {
 };
 
 
-// Node prep of the clamp in the fit (one node chunk, S <= CLAMP_LDS_SPECS) as workgroups
-// behind a reduce launch's (KCC_NP_IN_REDUCE): n_place workgroups of spec_place (after the
-// zero_only rank workgroup's flag), then n_rows workgroups of 1024 rows each (node_prep's
-// clamp-in-fit work, after every reduce wave has signalled).  The reduce's node sums go
+// Node prep of the clamp in the fit (one node chunk, S <= CLAMP_LDS_SPECS, not dense, at
+// least one node and one container) as workgroups behind a reduce launch's: n_place
+// workgroups of spec_place (after the zero_only rank workgroup's flag), then n_rows
+// workgroups of 1024 rows each (np_rows: the row pass it shares with node_prep_kernel, each
+// after the reduce waves that store its rows have signalled).  Every call with the clamp in
+// the fit runs it here; node_prep_kernel serves the clamp-correction layout alone.  The reduce's node sums go
 // out write-through (sc1) and each reduce wave adds 1 to sync[16] when done (its stores
 // performed); the node-prep workgroups read them at agent scope.  The last of them resets
 // the sync words.  Dispatch order makes the waits safe: on every XCD all the reduce's
@@ -401,6 +403,7 @@ constexpr int64_t RED_RANKS_LAST_MIN = (int64_t)16 << 20;
 // passes), call_nodes: the call's rows (its pass size, clamp_pass_rows).
 // Needs the sorted spec arrays (spec_rank's) on the stream before it.  place != nullptr:
 // spec_place runs as extra workgroups of this launch (place->n_blocks is set here).
+// The clamp-correction layout only: a call with the clamp in the fit launches none (below).
 hipError_t launch_node_prep(int64_t n_nodes, const uint64_t* alloc_cpu,
                             const int64_t* alloc_mem, const int64_t* alloc_pods,
                             const int64_t* pod_count, const uint64_t* used_cpu,
@@ -408,10 +411,11 @@ hipError_t launch_node_prep(int64_t n_nodes, const uint64_t* alloc_cpu,
                             SlowNode* slow, int64_t* slow_list, int64_t n_specs, ClampWork cw,
                             unsigned long long* counters, int chunk, int64_t row0,
                             int64_t call_nodes, hipStream_t s, bool dense = false,
-                            const PlaceArgs* place = nullptr, int32_t* fast_cl = nullptr);
-// Clamp in the fit (fast_cl != nullptr; one node chunk, S <= CLAMP_LDS_SPECS, not dense):
-// node_prep streams each row's clamp value (allocatable pods - pod count, CC:135) beside
-// its FitGroupA (fast_cl[row position]) and builds no clamp tables; the fit computes the
+                            const PlaceArgs* place = nullptr);
+// Clamp in the fit (one node chunk, S <= CLAMP_LDS_SPECS, not dense, at least one node and
+// one container; no launch_node_prep): node prep in the reduce launch (NpArgs) streams each
+// row's clamp value (allocatable pods - pod count, CC:135) beside its FitGroupA
+// (fast_cl[row position]) and builds no clamp tables; the fit (fast_cl != nullptr) computes the
 // reference's x >= P ? clamp : x itself (5 VALU per node x wave instead of 3) and
 // subtracts counters[CNT_CLAMP_ALL] from every normal spec; no clamp_apply launch.  The
 // choice for small shards, where clamp_apply's fixed cost exceeds the fit's extra issue.

@@ -254,11 +254,6 @@ __device__ void np_body(const NpArgs& np, int32_t j, uint32_t* scratch);
 
 // NPM: node prep behind the reduce's workgroups (NpArgs): the node sums written through
 // (sc1) and every wave's completion counted
-#ifdef KCC_DIAG_NP_NOSYNC  // timing diagnostics only (wrong results): node prep does not wait
-constexpr bool KCC_NP_NOSYNC = true;
-#else
-constexpr bool KCC_NP_NOSYNC = false;
-#endif
 #ifdef KCC_DIAG_NP_NOSC1  // timing diagnostics only: the node sums stored plainly
 constexpr bool KCC_NP_NOSC1 = true;
 #else
@@ -307,7 +302,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(RedArgs a, RankArgs ra, NpA
   // wave's flag); the wave's stores performed, then its flag
   const uint32_t epoch = NPM ? __hip_atomic_load(np.sync + NP_EPOCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u : 0u;
   auto red_signal = [&]() {
-    if constexpr (NPM && !KCC_NP_NOSYNC) {
+    if constexpr (NPM) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if ((threadIdx.x & 63) == 0)
         __hip_atomic_store(np.sync + NP_FLAGS + w, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -686,10 +681,142 @@ __device__ void np_wait_rows(const NpArgs& np, int64_t i0, int64_t i1, uint32_t 
   __syncthreads();
 }
 
-// 1024 rows (thread t: rows i0 + t + 256 q): node_prep's clamp-in-fit work (NC, one node
-// chunk; see node_prep_kernel): the free capacity, the slow rows, the node stream (one
-// stream position per workgroup, the rows padded to whole groups), the clamp values, and
-// the rows clamped for every spec
+// ---- node prep's row pass: the steps np_rows (in the reduce launch) and node_prep_kernel
+// (its own launch) share; each loads the rows its own way ----------------------------------
+
+// the class counts from spec_rank's / spec_place's per-block counts, summed by every wave
+// (one load per lane at S <= 4096).  AGENT: agent-scope loads (written in this launch)
+struct NpClasses {
+  bool want_b;    // class-B specs exist
+  int64_t nN;     // normal specs
+  bool slow_all;  // exact-path specs exist
+};
+template <bool AGENT>
+__device__ __forceinline__ NpClasses np_classes(const uint32_t* bcnt, int64_t S, int lane) {
+  uint64_t cls_n = 0;  // class A | class B << 32
+  const unsigned long long* bc = reinterpret_cast<const unsigned long long*>(bcnt);
+  for (int64_t b = lane; b < (S + 63) / 64; b += 64)
+    cls_n += AGENT ? __hip_atomic_load(bc + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : bc[b];
+  cls_n = readlane_u64(wave_incl_scan_u64(cls_n), 63);
+  NpClasses c;
+  c.want_b = (cls_n >> 32) != 0;
+  c.nN = (int64_t)(uint32_t)cls_n + (int64_t)(cls_n >> 32);
+  c.slow_all = c.nN < S;
+  return c;
+}
+
+// One row's stream entry (fm, fc, P, cl): free memory < 2^50, free cpu < 2^23, P and the
+// clamp value of a row within the fast-path bounds (returns true), else zeros.  Writes the
+// row's SlowNode when it is slow, or when exact-path specs exist (slow_all: their waves walk
+// all rows).  (The entry leaves through references, not as a struct: with a struct the four
+// values merge in another order after the branch, and node_prep_kernel's SUB = 4
+// instantiations spill 68 to 120 bytes instead of 28 to 56.)
+__device__ __forceinline__ bool np_classify(bool valid, int64_t i, uint64_t alloc_cpu, uint64_t used_cpu,
+                                            int64_t alloc_mem, int64_t used_mem, int64_t alloc_pods,
+                                            int64_t pod_count, bool slow_all, SlowNode* __restrict__ slow,
+                                            uint64_t& r_fm, uint32_t& r_fc, int32_t& r_P, int32_t& r_cl) {
+  bool ok = false;
+  r_fm = 0;
+  r_fc = 0;
+  r_P = 0;
+  r_cl = 0;
+  if (valid) {
+    const uint64_t fc = alloc_cpu > used_cpu ? alloc_cpu - used_cpu : 0;                                 // CC:119-123
+    const int64_t fm = alloc_mem > used_mem ? (int64_t)((uint64_t)alloc_mem - (uint64_t)used_mem) : 0;  // CC:125-129
+    const int64_t P = alloc_pods;
+    const int64_t cl = (int64_t)((uint64_t)P - (uint64_t)pod_count);                                    // CC:135
+    ok = fc < FAST_FC_MAX && fm >= 0 && fm < FAST_FM_MAX && P >= -FAST_P_ABS && P <= FAST_P_ABS &&
+         cl >= -FAST_CL_ABS && cl <= FAST_CL_ABS;
+    if (ok) {
+      r_fm = (uint64_t)fm;
+      r_fc = (uint32_t)fc;
+      r_P = (int32_t)P;
+      r_cl = (int32_t)cl;
+    }
+    if (slow_all || !ok) {
+      SlowNode sn;
+      sn.fc = fc;
+      sn.fm = fm;
+      sn.P = P;
+      sn.cl = cl;
+      slow[i] = sn;
+    }
+  }
+  return ok;
+}
+
+// the wave's slow rows appended to slow_list: one returning atomic per wave on *count
+__device__ __forceinline__ void np_slow_append(bool is_slow, int64_t i, int lane, unsigned long long* count,
+                                               int64_t* __restrict__ slow_list) {
+  const unsigned long long bl = __ballot(is_slow);
+  if (bl) {
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(count, (unsigned long long)__popcll(bl));
+    base = __shfl(base, 0);
+    if (is_slow) slow_list[base + __popcll(bl & ((1ull << lane) - 1ull))] = i;
+  }
+}
+
+// the wave's sum of the weights of its rows clamped for every spec (P <= 0), wave-uniform
+// (by reference: by value, node_prep_kernel converts each row's P to f64 as a 64-bit value,
+// three more VALU per row)
+__device__ __forceinline__ uint64_t np_always_sum(const uint64_t& sum) {
+  uint64_t v = sum;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// The workgroup's stream position, rows padded to whole groups: each wave's lane 0 leaves
+// its streamed rows (np_wave_streamed) in wc[wave]; after a barrier thread 0 claims the
+// workgroup's total, np_wc_sum(wc, waves), with one returning atomic on *count
+// (np_stream_claim) and publishes the result through LDS — np_rows at once,
+// node_prep_kernel after its last phase 2, so the atomic is in flight meanwhile; after that
+// barrier wave wv's rows start np_wc_sum(wc, wv) rows past the claim.
+template <int SUB>
+__device__ __forceinline__ uint32_t np_wave_streamed(const unsigned long long (&sbal)[SUB]) {
+  uint32_t n = 0;
+#pragma unroll
+  for (int q = 0; q < SUB; ++q) n += (uint32_t)__popcll(sbal[q]);
+  return n;
+}
+__device__ __forceinline__ uint32_t np_padded(uint32_t tot) { return (tot + FIT_GROUP - 1) / FIT_GROUP * FIT_GROUP; }
+__device__ __forceinline__ uint32_t np_wc_sum(const uint32_t* wc, int waves) {
+  uint32_t n = 0;
+  for (int u = 0; u < waves; ++u) n += wc[u];
+  return n;
+}
+__device__ __forceinline__ uint64_t np_stream_claim(uint32_t tot, unsigned long long* count) {
+  const uint32_t padded = np_padded(tot);
+  return padded ? atomicAdd(count, (unsigned long long)padded) : 0ull;
+}
+
+// One stream entry (CL: with its clamp value, the clamp in the fit).
+// (non-temporal stores here, so fewer dirty lines wait for the end-of-kernel write-back,
+// measured: C4 step 0.2895 -> 0.3171 ms — the rows' scattered partial-group stores then
+// reach HBM one by one — 8-way rank 0.0594 -> 0.0582; round 5, profiles/r05_ab_np_nt.txt)
+#define NP_ST(ref, v) ((ref) = (v))
+template <bool CL>
+__device__ __forceinline__ void np_put(uint64_t pos, uint64_t fmv, uint32_t fcv, uint32_t Pv, int32_t clv,
+                                       FitGroupA* __restrict__ fast_a, FitGroup* __restrict__ fast_b,
+                                       bool want_b, int32_t* __restrict__ fast_cl) {
+  const int kk = (int)(pos % FIT_GROUP);
+  if constexpr (CL) NP_ST(fast_cl[pos], clv);
+  FitGroupA& a = fast_a[pos / FIT_GROUP];
+  NP_ST(a.fm[kk], fmv);
+  NP_ST(a.fc[kk], fcv);
+  NP_ST(a.P[kk], Pv);
+  if (want_b) {
+    FitGroup& g = fast_b[pos / FIT_GROUP];
+    NP_ST(g.fc[kk], (double)fcv);            // exact
+    NP_ST(g.fm[kk], (double)fmv);            // exact (< 2^50)
+    NP_ST(g.Pb[kk], FIT_BIAS + (double)Pv);  // exact (P <= 2^20)
+  }
+}
+
+// 1024 rows (thread t: rows i0 + t + 256 q) of the clamp in the fit (one node chunk): the
+// free capacity, the slow rows, the node stream (one stream position per workgroup, the
+// rows padded to whole groups) with the clamp values, and the rows clamped for every spec
 __device__ void np_rows(const NpArgs& np, int32_t rb, uint32_t* scratch) {
   constexpr int SUB = NP_ROWS_PER_WG / 256;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -710,17 +837,8 @@ __device__ void np_rows(const NpArgs& np, int32_t rb, uint32_t* scratch) {
   const uint32_t epoch = __hip_atomic_load(np.sync + NP_EPOCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
   np_wait(np.sync + NP_DONE, epoch, np.faults);  // the counters zeroed, the class counts written
   KCC_TL(rb % 1024, 6);
-  uint64_t cls_n = 0;  // class A | class B << 32
-  {
-    const unsigned long long* bc = reinterpret_cast<const unsigned long long*>(np.bcnt);
-    for (int64_t b = lane; b < (np.S + 63) / 64; b += 64)
-      cls_n += __hip_atomic_load(bc + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    cls_n = readlane_u64(wave_incl_scan_u64(cls_n), 63);
-  }
-  const bool want_b = (cls_n >> 32) != 0;
-  const int64_t nN = (int64_t)(uint32_t)cls_n + (int64_t)(cls_n >> 32);
-  const bool slow_all = nN < np.S;
-  if (!KCC_NP_NOSYNC) np_wait_rows(np, i0, i0 + NP_ROWS_PER_WG < n ? i0 + NP_ROWS_PER_WG : n, epoch);  // the rows' sums stored
+  const NpClasses cls = np_classes<true>(np.bcnt, np.S, lane);
+  np_wait_rows(np, i0, i0 + NP_ROWS_PER_WG < n ? i0 + NP_ROWS_PER_WG : n, epoch);  // the rows' sums stored
   KCC_TL(rb % 1024, 3);
   uint64_t uc[SUB];
   int64_t um[SUB];
@@ -740,92 +858,37 @@ __device__ void np_rows(const NpArgs& np, int32_t rb, uint32_t* scratch) {
   for (int q = 0; q < SUB; ++q) {
     const int64_t i = i0 + q * 256 + tid;
     const bool valid = i < n;
-    bool ok = false;
-    r_fm[q] = 0;
-    r_fc[q] = 0;
-    r_P[q] = 0;
-    r_cl[q] = 0;
-    if (valid) {
-      const uint64_t fc = ac[q] > uc[q] ? ac[q] - uc[q] : 0;                                      // CC:119-123
-      const int64_t fm = am[q] > um[q] ? (int64_t)((uint64_t)am[q] - (uint64_t)um[q]) : 0;       // CC:125-129
-      const int64_t P = aP[q];
-      const int64_t cl = (int64_t)((uint64_t)P - (uint64_t)pc[q]);                               // CC:135
-      ok = fc < FAST_FC_MAX && fm >= 0 && fm < FAST_FM_MAX && P >= -FAST_P_ABS && P <= FAST_P_ABS &&
-           cl >= -FAST_CL_ABS && cl <= FAST_CL_ABS;
-      if (ok) {
-        r_fm[q] = (uint64_t)fm;
-        r_fc[q] = (uint32_t)fc;
-        r_P[q] = (int32_t)P;
-        r_cl[q] = (int32_t)cl;
-        if (nN > 0 && P <= 0) always_sum += (uint64_t)(0 - cl);  // x >= P for every spec: w = Penc - cl
-      }
-      if (slow_all || !ok) {
-        SlowNode sn;
-        sn.fc = fc;
-        sn.fm = fm;
-        sn.P = P;
-        sn.cl = cl;
-        np.slow[i] = sn;
-      }
-    }
-    const unsigned long long bl = __ballot(valid && !ok);
-    if (bl) {
-      unsigned long long base = 0;
-      if (lane == 0) base = atomicAdd(&np.counters[CNT_SLOW_ROWS], (unsigned long long)__popcll(bl));
-      base = __shfl(base, 0);
-      if (valid && !ok) np.slow_list[base + __popcll(bl & ((1ull << lane) - 1ull))] = i;
-    }
+    const bool ok = np_classify(valid, i, ac[q], uc[q], am[q], um[q], aP[q], pc[q], cls.slow_all, np.slow,
+                                r_fm[q], r_fc[q], r_P[q], r_cl[q]);
+    // x >= P for every spec: w = max(P, 0) - cl
+    if (ok && cls.nN > 0 && r_P[q] <= 0) always_sum += (uint64_t)(0 - (int64_t)r_cl[q]);
+    np_slow_append(valid && !ok, i, lane, &np.counters[CNT_SLOW_ROWS], np.slow_list);
     sbal[q] = __ballot(r_fc[q] > 0 && r_fm[q] > 0 && r_P[q] > 0);  // 0 unless ok
   }
   KCC_TL(rb % 1024, 4);
   {  // rows clamped for every spec: one wave-summed add (one per workgroup: equal, round 5)
-    uint64_t v = always_sum;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    const uint64_t v = np_always_sum(always_sum);
     if (lane == 0 && v) atomicAdd(&np.counters[CNT_CLAMP_ALL], (unsigned long long)v);
   }
-  // the workgroup's stream position: one returning atomic, rows padded to whole groups
-  uint32_t* np_wc = scratch;                                       // [4]
+  uint32_t* np_wc = scratch;  // [4]
   unsigned long long* np_base = reinterpret_cast<unsigned long long*>(scratch + 8);
-  uint32_t wave_streamed = 0;
-#pragma unroll
-  for (int q = 0; q < SUB; ++q) wave_streamed += (uint32_t)__popcll(sbal[q]);
-  if (lane == 0) np_wc[wv] = wave_streamed;
+  if (lane == 0) np_wc[wv] = np_wave_streamed(sbal);
   __syncthreads();
-  const uint32_t tot = np_wc[0] + np_wc[1] + np_wc[2] + np_wc[3];
-  if (tid == 0) {
-    const uint32_t padded = (tot + FIT_GROUP - 1) / FIT_GROUP * FIT_GROUP;
-    *np_base = padded ? atomicAdd(&np.counters[CNT_STREAM], (unsigned long long)padded) : 0ull;
-  }
+  const uint32_t tot = np_wc_sum(np_wc, 4);
+  if (tid == 0) *np_base = np_stream_claim(tot, &np.counters[CNT_STREAM]);
   __syncthreads();
   KCC_TL(rb % 1024, 5);
-  uint32_t before = 0;
-  for (int u = 0; u < wv; ++u) before += np_wc[u];
-  const uint64_t base = *np_base;
-  auto put = [&](uint64_t pos, uint64_t fmv, uint32_t fcv, uint32_t Pv, int32_t clv) {
-    const int kk = (int)(pos % FIT_GROUP);
-    np.fast_cl[pos] = clv;
-    FitGroupA& g = np.fast_a[pos / FIT_GROUP];
-    g.fm[kk] = fmv;
-    g.fc[kk] = fcv;
-    g.P[kk] = Pv;
-    if (want_b) {
-      FitGroup& gb = np.fast_b[pos / FIT_GROUP];
-      gb.fc[kk] = (double)fcv;             // exact
-      gb.fm[kk] = (double)fmv;             // exact (< 2^50)
-      gb.Pb[kk] = FIT_BIAS + (double)Pv;   // exact (P <= 2^20)
-    }
-  };
+  const uint64_t base = *np_base, sb0 = base + np_wc_sum(np_wc, wv);
   uint32_t done = 0;
 #pragma unroll
   for (int q = 0; q < SUB; ++q) {
     if ((sbal[q] >> lane) & 1ull)
-      put(base + before + done + (uint32_t)__popcll(sbal[q] & ((1ull << lane) - 1ull)), r_fm[q], r_fc[q],
-          (uint32_t)r_P[q], r_cl[q]);
+      np_put<true>(sb0 + done + (uint32_t)__popcll(sbal[q] & ((1ull << lane) - 1ull)), r_fm[q], r_fc[q],
+                   (uint32_t)r_P[q], r_cl[q], np.fast_a, np.fast_b, cls.want_b, np.fast_cl);
     done += (uint32_t)__popcll(sbal[q]);
   }
-  const uint32_t pad = (tot + FIT_GROUP - 1) / FIT_GROUP * FIT_GROUP - tot;
-  if ((uint32_t)tid < pad) put(base + tot + tid, 0ull, 0u, 0u, 0);  // the last group's padding
+  if ((uint32_t)tid < np_padded(tot) - tot)  // the last group's padding
+    np_put<true>(base + tot + tid, 0ull, 0u, 0u, 0, np.fast_a, np.fast_b, cls.want_b, np.fast_cl);
   KCC_TL(rb % 1024, 1);
 }
 
@@ -963,10 +1026,7 @@ __host__ __device__ inline uint32_t np_stride(int64_t S) {  // smallest power of
 // carries only its own path's registers).  A pass is SUB x 1024 rows (clamp_pass_rows(n)
 // of the call), worked on in SUB sub-steps of one row per thread; each sub-step's rows
 // are loaded while the previous one is worked on.
-// NC: the clamp in the fit (launch_node_prep's fast_cl; MODE 2 only): no search or count
-// tables, no clamp cells or records; each streamed row's clamp value goes to fast_cl and the
-// rows clamped for every spec sum into counters[CNT_CLAMP_ALL].
-template <int MODE, int SUB, bool NC>
+template <int MODE, int SUB>
 __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t n, const uint64_t* __restrict__ alloc_cpu,
                                  const int64_t* __restrict__ alloc_mem,
                                  const int64_t* __restrict__ alloc_pods,
@@ -977,9 +1037,7 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
                                  SlowNode* __restrict__ slow, int64_t* __restrict__ slow_list,
                                  int64_t S, ClampWork cw,
                                  unsigned long long* __restrict__ counters,
-                                 int32_t chunk, int32_t dense, int64_t pass0, PlaceArgs pa,
-                                 int32_t* __restrict__ fast_cl) {
-  static_assert(!NC || MODE == 2, "the clamp in the fit: S <= CLAMP_LDS_SPECS only");
+                                 int32_t chunk, int32_t dense, int64_t pass0, PlaceArgs pa) {
   if ((int32_t)blockIdx.x < pa.n_blocks) {  // spec_place's workgroups, in front (MODE 2)
     spec_place_body(pa, blockIdx.x);
     return;
@@ -1012,17 +1070,10 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
   __shared__ uint32_t np_tot;
   __shared__ uint32_t np_bcnt[NP_BINS];                 // binned records per bin (this pass)
   __shared__ uint32_t np_bstart[NP_BINS];               // their exclusive prefix
-  // the class counts from spec_rank's per-block counts (spec_place may run beside this
-  // launch): every wave sums them (one load per lane at S <= 4096)
-  uint64_t cls_n = 0;  // class A | class B << 32
-  {
-    const uint64_t* bc = reinterpret_cast<const uint64_t*>(cw.bcnt);
-    for (int64_t b = lane; b < (S + 63) / 64; b += 64) cls_n += bc[b];
-    cls_n = readlane_u64(wave_incl_scan_u64(cls_n), 63);
-  }
-  const bool want_b = (cls_n >> 32) != 0;                       // class-B specs exist
-  const int64_t nN = (int64_t)(uint32_t)cls_n + (int64_t)(cls_n >> 32);  // normal specs
-  const bool slow_all = nN < S;                    // exact-path specs exist
+  // the class counts from spec_rank's per-block counts (spec_place may run beside this launch)
+  const NpClasses cls = np_classes<false>(cw.bcnt, S, lane);
+  const bool want_b = cls.want_b, slow_all = cls.slow_all;
+  const int64_t nN = cls.nN;
   const int64_t T = (nN + 63) / 64, W = T + 2;
   // T <= CLAMP_BIN_T_MAX (always at S <= 4096: MODE 2 carries no table atomics)
   const bool binned = MODE == 2 || clamp_binned(S);
@@ -1052,7 +1103,7 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
   for (int b = threadIdx.x; b < NP_BINS; b += KCC_NODE_PREP_BLOCK) np_bcnt[b] = 0;
   constexpr int PER = (int)(CLAMP_LDS_SPECS / KCC_NODE_PREP_BLOCK);
   uint32_t yv[PER];  // y-rank of x-rank tid + 1024 u
-  if (srch && !NC) {
+  if (srch) {
     // the sorted requests (spec_rank's last arrivers write them): every load first, guarded by S (a kernel argument) rather than nN, so they
     // travel with the class counts' load (one memory round trip); entries nN.. are masked
     uint64_t cv[PER], mv[PER];
@@ -1078,7 +1129,7 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
   }
   __syncthreads();  // masks zero
   KCC_TL(bid % 1024, 6);
-  if (lds && !NC) {
+  if (lds) {
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const int64_t x = threadIdx.x + (int64_t)KCC_NODE_PREP_BLOCK * u;
@@ -1091,11 +1142,11 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
   KCC_TL(bid % 1024, 7);
   // smallest normal requests (rows below either dominate no spec): the tables' first
   // entries (+inf when there are none; cs[0] >= 1; MODE 1's LDS tables are sampled)
-  const uint32_t cmin = NC ? 0u : lds ? cs_l[np_slot(0u)]
+  const uint32_t cmin = lds ? cs_l[np_slot(0u)]
                             : (nN > 0 ? (cw.cs[0] < FAST_FC_MAX ? (uint32_t)cw.cs[0] : 0xffffffffu)
                                       : 0xffffffffu);
-  const int64_t mmin = NC ? 0 : lds ? ms_l[np_slot(0u)] : (nN > 0 ? cw.ms[0] : INT64_MAX);
-  if (lds && !NC) {  // the prefix counts: row g along Y and column Y = g along G, lane = index;
+  const int64_t mmin = lds ? ms_l[np_slot(0u)] : (nN > 0 ? cw.ms[0] : INT64_MAX);
+  if (lds) {  // the prefix counts: row g along Y and column Y = g along G, lane = index;
     // rows g and g + 16 in one 32-bit scan of four byte fields (each count and prefix is
     // a member count of one x-group or y-block, <= 64: no carries between the bytes)
     static_assert(KCC_NODE_PREP_BLOCK == 1024, "16 waves: rows wv, wv + 16, wv + 32, wv + 48");
@@ -1135,7 +1186,6 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
     uint64_t r_fm[SUB];
     uint32_t r_fc[SUB];
     int32_t r_P[SUB];
-    int32_t r_cl[SUB];  // NC: the clamp value of a streamed row
     unsigned long long sbal[SUB];
     uint32_t pk1[SUB], pk2[SUB], pk3[SUB];
     uint64_t always_sum = 0;
@@ -1146,43 +1196,10 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
       const int64_t i = i0 + q * KCC_NODE_PREP_BLOCK + threadIdx.x;
       const bool valid = i < n;
       // phase 1: the free capacity, the slow rows; the 64-bit loads die here
-      bool ok = false;
-      int32_t cl_q = 0;
-      r_fm[q] = 0;
-      r_fc[q] = 0;
-      r_P[q] = 0;
-      if (valid) {
-        const uint64_t fc = ld_ac > ld_uc ? ld_ac - ld_uc : 0;                                 // CC:119-123
-        const int64_t fm = ld_am > ld_um ? (int64_t)((uint64_t)ld_am - (uint64_t)ld_um) : 0;  // CC:125-129
-        const int64_t P = ld_P;
-        const int64_t cl = (int64_t)((uint64_t)P - (uint64_t)ld_pc);                          // CC:135
-        ok = fc < FAST_FC_MAX && fm >= 0 && fm < FAST_FM_MAX && P >= -FAST_P_ABS &&
-             P <= FAST_P_ABS && cl >= -FAST_CL_ABS && cl <= FAST_CL_ABS;
-        if (ok) {
-          r_fm[q] = (uint64_t)fm;
-          r_fc[q] = (uint32_t)fc;
-          r_P[q] = (int32_t)P;
-          cl_q = (int32_t)cl;
-        }
-        if (slow_all || !ok) {
-          SlowNode sn;
-          sn.fc = fc;
-          sn.fm = fm;
-          sn.P = P;
-          sn.cl = cl;
-          slow[i] = sn;
-        }
-      }
-      {
-        const unsigned long long bl = __ballot(valid && !ok);
-        if (bl) {
-          unsigned long long base = 0;
-          if (lane == 0)
-            base = atomicAdd(&counters[CNT_SLOW_ROWS + chunk], (unsigned long long)__popcll(bl));
-          base = __shfl(base, 0);
-          if (valid && !ok) slow_list[base + __popcll(bl & ((1ull << lane) - 1ull))] = i;
-        }
-      }
+      int32_t cl_q;
+      const bool ok = np_classify(valid, i, ld_ac, ld_uc, ld_am, ld_um, ld_P, ld_pc, slow_all, slow,
+                                  r_fm[q], r_fc[q], r_P[q], cl_q);
+      np_slow_append(valid && !ok, i, lane, &counters[CNT_SLOW_ROWS + chunk], slow_list);
       // the next sub-step's row (the load registers are free now)
       load_row(q + 1 < SUB ? i + KCC_NODE_PREP_BLOCK : i0 + stride + threadIdx.x);
       // the fit's node stream: the rows with something to add
@@ -1190,15 +1207,11 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
       if (q == SUB - 1) {
         // every sub-step's ballots are known: the pass's stream position (one returning
         // atomic by thread 0) is in flight during the last phase 2
-        uint32_t wave_streamed = 0;
-#pragma unroll
-        for (int q2 = 0; q2 < SUB; ++q2) wave_streamed += (uint32_t)__popcll(sbal[q2]);
-        if (lane == 0) np_wc[wv] = wave_streamed;
+        if (lane == 0) np_wc[wv] = np_wave_streamed(sbal);
         __syncthreads();  // np_wc
         if (threadIdx.x == 0) {
-          for (int u = 0; u < KCC_NODE_PREP_BLOCK / 64; ++u) t_pass += np_wc[u];
-          const uint32_t padded = (t_pass + FIT_GROUP - 1) / FIT_GROUP * FIT_GROUP;  // whole groups
-          if (padded) base_ret = atomicAdd(&counters[CNT_STREAM + chunk], (unsigned long long)padded);
+          t_pass = np_wc_sum(np_wc, KCC_NODE_PREP_BLOCK / 64);
+          base_ret = np_stream_claim(t_pass, &counters[CNT_STREAM + chunk]);
         }
         KCC_TL(bid % 1024, 3);
       }
@@ -1211,10 +1224,6 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
       const int64_t P = r_P[q], Penc = P > 0 ? P : 0;
       const int64_t wfull = Penc - (int64_t)cl_q;  // contribution = min(x, Penc) - w when clamped
       if (ok && nN > 0 && P <= 0) always_sum += (uint64_t)wfull;  // x >= P for every spec
-      r_cl[q] = cl_q;
-      if constexpr (NC) {
-        pk1[q] = pk2[q] = pk3[q] = 0u;
-      } else {
       const double rP = recip_up_f64(P > 0 ? (uint64_t)P : 1ull);
       const int64_t V0 = (int64_t)((double)r_fm[q] * rP);  // floor(fm / P): exact (§5)
       const uint32_t U0 = (uint32_t)((double)r_fc[q] * rP);
@@ -1286,20 +1295,13 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
       pk1[q] = (rec2 ? k * 64 + rx : 0u) | (rec3 ? j * 64 + ry : 0u) << 13 | (wu & 63u) << 26;
       pk2[q] = rk2 | rk3 << 13 | ((wu >> 6) & 63u) << 26;
       pk3[q] = bin2 | bin3 << 9 | (uint32_t)((int32_t)wu >> 12) << 18;
-      }  // (!NC)
       // the scheduler keeps each sub-step to itself (hoisting the next one's work
       // across this point ran the SUB = 4 kernels out of registers)
       __builtin_amdgcn_sched_barrier(0);
     }
     {  // rows clamped for every spec: one wave-summed add into C[T+1][T+1]
-      uint64_t v = always_sum;
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      if (NC) {
-        if (lane == 0 && v) atomicAdd(&counters[CNT_CLAMP_ALL], (unsigned long long)v);
-      } else if (lane == 0 && v) {
-        c_add((T + 1) * W + T + 1, (int64_t)v);
-      }
+      const uint64_t v = np_always_sum(always_sum);
+      if (lane == 0 && v) c_add((T + 1) * W + T + 1, (int64_t)v);
     }
     if (threadIdx.x == 0) {
       np_base = base_ret;
@@ -1307,7 +1309,7 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
     }
     __syncthreads();  // np_base, and every record's rank
     KCC_TL(bid % 1024, 4);
-    if (binned && !NC && wv == 1) {
+    if (binned && wv == 1) {
       // the bins' starts: runs of per bins per lane, a shuffle scan of the run totals;
       // the pass's directory row (starts + total) goes out here, the counters return to 0
       const int per = (NB + 63) / 64;
@@ -1333,36 +1335,15 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
     }
     __syncthreads();
     {
-      uint32_t before = 0;
-      for (int u = 0; u < wv; ++u) before += np_wc[u];
-      const uint64_t sb0 = np_base + before;
+      const uint64_t sb0 = np_base + np_wc_sum(np_wc, wv);
       const uint32_t tot = np_tot;
-      const uint32_t pad = (tot + FIT_GROUP - 1) / FIT_GROUP * FIT_GROUP - tot;
-// (non-temporal stores here, so fewer dirty lines wait for the end-of-kernel write-back,
-// measured: C4 step 0.2895 -> 0.3171 ms — the rows' scattered partial-group stores then
-// reach HBM one by one — 8-way rank 0.0594 -> 0.0582; round 5, profiles/r05_ab_np_nt.txt)
-#define NP_ST(ref, v) ((ref) = (v))
-      auto put = [&](uint64_t pos, uint64_t fmv, uint32_t fcv, uint32_t Pv, int32_t clv) {
-        const int kk = (int)(pos % FIT_GROUP);
-        if (NC) NP_ST(fast_cl[pos], clv);
-        FitGroupA& a = fast_a[pos / FIT_GROUP];
-        NP_ST(a.fm[kk], fmv);
-        NP_ST(a.fc[kk], fcv);
-        NP_ST(a.P[kk], Pv);
-        if (want_b) {
-          FitGroup& g = fast_b[pos / FIT_GROUP];
-          NP_ST(g.fc[kk], (double)fcv);                      // exact
-          NP_ST(g.fm[kk], (double)fmv);                      // exact (< 2^50)
-          NP_ST(g.Pb[kk], FIT_BIAS + (double)Pv);            // exact (P <= 2^20)
-        }
-      };
       uint32_t done = 0;  // streamed rows of this wave's earlier sub-steps
       uint64_t* prec = cw.rec + pass * (2 * PR);
 #pragma unroll
       for (int q = 0; q < SUB; ++q) {
         if ((sbal[q] >> lane) & 1ull)  // P <= 0 streams only in the dense layout, as P = 0
-          put(sb0 + done + (uint32_t)__popcll(sbal[q] & ((1ull << lane) - 1ull)), r_fm[q], r_fc[q],
-              r_P[q] > 0 ? (uint32_t)r_P[q] : 0u, r_cl[q]);
+          np_put<false>(sb0 + done + (uint32_t)__popcll(sbal[q] & ((1ull << lane) - 1ull)), r_fm[q], r_fc[q],
+                        r_P[q] > 0 ? (uint32_t)r_P[q] : 0u, 0, fast_a, fast_b, want_b, nullptr);
         done += (uint32_t)__popcll(sbal[q]);
         const uint32_t c2 = pk1[q] & 0x1fffu, c3 = (pk1[q] >> 13) & 0x1fffu;
         if (c2 | c3) {
@@ -1372,12 +1353,13 @@ __global__ __launch_bounds__(KCC_NODE_PREP_BLOCK) void node_prep_kernel(int64_t 
           if (c3) NP_ST(prec[np_bstart[(pk3[q] >> 9) & 0x1ffu] + ((pk2[q] >> 13) & 0x1fffu)], wbits | c3);
         }
       }
-      if (threadIdx.x < pad) put(np_base + tot + threadIdx.x, 0ull, 0u, 0u, 0);  // the last group's padding
+      if (threadIdx.x < np_padded(tot) - tot)  // the last group's padding
+        np_put<false>(np_base + tot + threadIdx.x, 0ull, 0u, 0u, 0, fast_a, fast_b, want_b, nullptr);
     }
     __syncthreads();  // np_wc / np_base / np_bstart are rewritten by the next pass
     KCC_TL(bid % 1024, 5);
   }
-  if (cpriv && !NC) {  // the private C into this workgroup's device copy: its non-zero cells
+  if (cpriv) {  // the private C into this workgroup's device copy: its non-zero cells
     for (int64_t e = threadIdx.x; e < W * W; e += KCC_NODE_PREP_BLOCK) {
       const unsigned long long v = c_l[e];
       if (v) np_atomic(&Cc[e], (int64_t)v);
@@ -2298,12 +2280,12 @@ __device__ __forceinline__ double f64_at(const i32x16& v, int k) {
 // the resident workgroups per column measured slower (round 3, prepare + run: C4 172 ->
 // 220 / 372 us, its 8-way shard 57 -> 63 / 83 us, profiles/r03o_ab_fit_grid.jsonl)
 #define KCC_FIT_ATTR __attribute__((amdgpu_waves_per_eu(8)))
-// NC: the clamp in the fit (fast_cl, launch_fit) — its own instantiation, so the
+// CL: the clamp in the fit (fast_cl, launch_fit) — its own instantiation, so the
 // clamp-correction layout's registers are not the larger loops' (one kernel holding both
 // spilled 52 SGPRs: C4 fit 116 -> 120 us)
 // (the body of fit_kernel; b = the workgroup's index in the fit's grid, q_slot = 2 words of
 // LDS)
-template <bool NC>
+template <bool CL>
 __device__ __forceinline__ void fit_body(
     int64_t n_nodes, uint32_t* __restrict__ queue, const FitGroupA* __restrict__ fast_a,
     const FitGroup* __restrict__ fast_b, const SlowNode* __restrict__ slow,
@@ -2468,7 +2450,7 @@ __device__ __forceinline__ void fit_body(
     set_round_nearest();
     acc += (uint64_t)(int64_t)acc32;
   };
-  // the clamp in the fit (fast_cl: launch_node_prep's NC mode): x >= P ? clamp : x per
+  // the clamp in the fit (fast_cl: node prep in the reduce launch, np_rows): x >= P ? clamp : x per
   // node (CC:133-136), the clamp value from fast_cl, P >= 1 on every streamed row (padding:
   // x = 0 >= P = 0, clamp 0).  Class A: 5.0 VALU per node, the clamp values by vector loads
   // (uniform addresses: one line per wave), so the select takes them as VGPRs.  By scalar
@@ -2595,7 +2577,7 @@ __device__ __forceinline__ void fit_body(
       const int cnt = (int)((cur + qcur < lim ? cur + qcur : lim) - cur);
       qcur = qn;
       if (wave_fast) {
-        if constexpr (NC) {
+        if constexpr (CL) {
           if (!wave_b) sum_a_nc(cur, cnt);
           else sum_b_nc(cur, cnt);
         } else {
@@ -2652,7 +2634,7 @@ __device__ __forceinline__ void fit_body(
   // the clamp in the fit: the rows clamped for every spec (P <= 0, never streamed), once
   // per spec (the column's workgroup by == 0) for the normal specs (exact waves walked
   // every row on the exact path)
-  if (NC && by == 0 && wave_fast) acc -= (uint64_t)counters[CNT_CLAMP_ALL];
+  if (CL && by == 0 && wave_fast) acc -= (uint64_t)counters[CNT_CLAMP_ALL];
   // a faulted device's partial carries the fault to every consumer (SPEC_FAULT_MARK)
   if (by == 0 && device_faulted(faults)) errs += SPEC_FAULT_MARK;
   if (active) {
@@ -2662,7 +2644,7 @@ __device__ __forceinline__ void fit_body(
   KCC_TL(2048 + b % 4096, 3);
 }
 
-template <bool NC>
+template <bool CL>
 __global__ __launch_bounds__(256) KCC_FIT_ATTR void fit_kernel(
     int64_t n_nodes, uint32_t* __restrict__ queue, const FitGroupA* __restrict__ fast_a,
     const FitGroup* __restrict__ fast_b, const SlowNode* __restrict__ slow,
@@ -2671,7 +2653,7 @@ __global__ __launch_bounds__(256) KCC_FIT_ATTR void fit_kernel(
     int32_t gx, int32_t gy, const int32_t* __restrict__ fast_cl,
     const unsigned long long* __restrict__ faults) {
   __shared__ uint32_t q_slot[2];
-  fit_body<NC>(n_nodes, queue, fast_a, fast_b, slow, slow_list, S, specs, partial, counters, chunk,
+  fit_body<CL>(n_nodes, queue, fast_a, fast_b, slow, slow_list, S, specs, partial, counters, chunk,
                gx, gy, fast_cl, faults, (int32_t)blockIdx.x, q_slot);
 }
 
@@ -2904,9 +2886,8 @@ hipError_t launch_node_prep(int64_t n_nodes, const uint64_t* alloc_cpu,
                             SlowNode* slow, int64_t* slow_list, int64_t n_specs,
                             ClampWork cw, unsigned long long* counters, int chunk, int64_t row0,
                             int64_t call_nodes, hipStream_t s, bool dense,
-                            const PlaceArgs* place, int32_t* fast_cl) {
+                            const PlaceArgs* place) {
   if (n_nodes <= 0 && !place) return hipSuccess;
-  if (fast_cl && (n_specs > CLAMP_LDS_SPECS || dense)) return hipErrorInvalidValue;
   const int64_t pr = clamp_pass_rows(call_nodes);
   if (row0 % pr != 0 || (pr != 1024 && pr != 4096)) return hipErrorInvalidValue;
   // one resident round of workgroups (LDS-bound at S <= CLAMP_LDS_SPECS: one per CU)
@@ -2916,13 +2897,11 @@ hipError_t launch_node_prep(int64_t n_nodes, const uint64_t* alloc_cpu,
     pa = *place;
     pa.n_blocks = (int32_t)((n_specs + KCC_NODE_PREP_BLOCK - 1) / KCC_NODE_PREP_BLOCK);
   }
-  const bool nc = fast_cl != nullptr;  // (mode 2)
-  const size_t lds_bytes = nc ? 0 : mode == 2 ? NODE_PREP_LDS : mode == 1 ? NODE_PREP_LDS_SRCH : 0;
-  auto kern = nc ? (pr == 1024 ? node_prep_kernel<2, 1, true> : node_prep_kernel<2, 4, true>)
-            : pr == 1024 ? (mode == 2 ? node_prep_kernel<2, 1, false> : mode == 1 ? node_prep_kernel<1, 1, false> : node_prep_kernel<0, 1, false>)
-                         : (mode == 2 ? node_prep_kernel<2, 4, false> : mode == 1 ? node_prep_kernel<1, 4, false> : node_prep_kernel<0, 4, false>);
-  static std::atomic<int64_t> resident[2][4][MAX_DEVS];
-  const int64_t res = resident_blocks(resident[pr == 1024 ? 0 : 1][nc ? 3 : mode],
+  const size_t lds_bytes = mode == 2 ? NODE_PREP_LDS : mode == 1 ? NODE_PREP_LDS_SRCH : 0;
+  auto kern = pr == 1024 ? (mode == 2 ? node_prep_kernel<2, 1> : mode == 1 ? node_prep_kernel<1, 1> : node_prep_kernel<0, 1>)
+                         : (mode == 2 ? node_prep_kernel<2, 4> : mode == 1 ? node_prep_kernel<1, 4> : node_prep_kernel<0, 4>);
+  static std::atomic<int64_t> resident[2][3][MAX_DEVS];
+  const int64_t res = resident_blocks(resident[pr == 1024 ? 0 : 1][mode],
                                       reinterpret_cast<const void*>(kern), KCC_NODE_PREP_BLOCK,
                                       lds_bytes, 256);
   const int64_t cap = res < NODE_PREP_GRID ? res : NODE_PREP_GRID;
@@ -2930,7 +2909,7 @@ hipError_t launch_node_prep(int64_t n_nodes, const uint64_t* alloc_cpu,
   hipLaunchKernelGGL(kern, dim3(np_blocks + (unsigned)pa.n_blocks), dim3(KCC_NODE_PREP_BLOCK),
                      lds_bytes, s, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
                      used_mem, fast_a, fast_b, slow, slow_list, n_specs, cw,
-                     counters, (int32_t)chunk, (int32_t)(dense ? 1 : 0), row0 / pr, pa, fast_cl);
+                     counters, (int32_t)chunk, (int32_t)(dense ? 1 : 0), row0 / pr, pa);
   return hipGetLastError();
 }
 

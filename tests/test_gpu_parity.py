@@ -456,6 +456,62 @@ def test_clamp_in_fit_modes(engine, mode, n, s, adv, zipf):
         engine.set_clamp_in_fit(-1)
 
 
+# (nodes, containers): none at all; one row; one row past a 1024-row pass; the same with one
+# container on the last node (a reduce of one wave: node prep rides behind it)
+NO_CONTAINER_SHAPES = [(0, 0), (1, 0), (1025, 0), (1025, 1)]
+
+
+@pytest.mark.parametrize("s", [1, 65])
+@pytest.mark.parametrize("mode", [-1, 0, 1])
+@pytest.mark.parametrize("n,n_cont", NO_CONTAINER_SHAPES)
+def test_clamp_in_fit_without_nodes_or_containers(engine, n, n_cont, mode, s):
+    """The clamp in the fit needs at least one node and one container (node prep then runs
+    behind the reduce's workgroups): a call without either applies the clamp by the
+    correction launch in every mode, and kcc_clamp_in_fit_used says so.  Totals == the
+    oracle either way, two calls in a row, through kcc_capacity_async and
+    kcc_capacity_partial_async + finalize; nodes without containers use nothing."""
+    import torch
+    c = synth.make_cluster(n, 20 * n, seed=47, chunk=1024, adversarial=True)
+    sc, sm = synth.make_specs(s, seed=47, adversarial=s > 1)  # (s == 1: a normal spec)
+    node_ptr = np.zeros(n + 1, np.int64)
+    node_ptr[n:] = n_cont  # (n_cont <= 1: on the last node)
+    cpu_req = np.full(n_cont, 250, np.uint64)
+    mem_req = np.full(n_cont, 3 << 28, np.int64)
+    dev = torch.device("cuda", 0)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)  # noqa: E731
+    used_cpu = torch.full((max(n, 1),), 7, dtype=torch.int64, device=dev)  # garbage
+    used_mem = torch.full((max(n, 1),), 7, dtype=torch.int64, device=dev)
+    partial = torch.empty(2 * s, dtype=torch.int64, device=dev)
+    totals = torch.empty(s, dtype=torch.int64, device=dev)
+    err = torch.empty(s, dtype=torch.int32, device=dev)
+    uc, um, _, _ = coracle.reduce_requests(node_ptr, cpu_req, mem_req, cpu_req, mem_req)
+    ot, oe = coracle.fit(c.alloc_cpu, c.alloc_mem, c.alloc_pods, c.pod_count, uc, um, sc, sm, NT)
+    args = (T(node_ptr), T(cpu_req), T(mem_req), T(c.alloc_cpu), T(c.alloc_mem),
+            T(c.alloc_pods), T(c.pod_count), used_cpu, used_mem, T(sc), T(sm))
+    stream = torch.cuda.Stream(dev)
+    engine.set_clamp_in_fit(mode)
+    try:
+        for k in range(2):
+            totals.fill_(-7)
+            with torch.cuda.stream(stream):
+                if k == 0:
+                    engine.capacity_async(node_ptr, *args, totals, err, stream=stream)
+                else:
+                    engine.capacity_partial_async(node_ptr, *args, partial, n_chunks=1, stream=stream)
+                    engine.fit_finalize_async(s, partial, totals, err, stream=stream)
+            stream.synchronize()
+            assert engine.clamp_in_fit_used() == (n_cont > 0 and mode != 0), f"call {k}"
+            np.testing.assert_array_equal(totals.cpu().numpy(), ot, err_msg=f"call {k}")
+            np.testing.assert_array_equal(err.cpu().numpy(), oe, err_msg=f"call {k}")
+            np.testing.assert_array_equal(used_cpu.cpu().numpy()[:n].view(np.uint64), uc, err_msg=f"call {k}")
+            np.testing.assert_array_equal(used_mem.cpu().numpy()[:n], um, err_msg=f"call {k}")
+            if n_cont == 0:
+                assert not used_cpu.cpu().numpy()[:n].any() and not used_mem.cpu().numpy()[:n].any()
+    finally:
+        engine.set_clamp_in_fit(-1)
+    assert engine.reduce_faults() == 0
+
+
 # ---- pipelined reduce + fit (node chunks, side stream) == host API ------------------------
 @pytest.mark.parametrize("n_chunks", [1, 2, 3, 4, 16])
 def test_pipelined_capacity_matches_host(engine, n_chunks):
