@@ -1749,6 +1749,7 @@ int kcc_count_by_key_async(kcc_ctx* ctx, int64_t n_keys, int64_t n, const int32_
   if (n_keys < 0 || n < 0) return fail(ctx, KCC_EINVAL, "negative size");
   if (n_keys > 0x7fffffff) return fail(ctx, KCC_EINVAL, "more than 2^31 - 1 keys");
   if ((n_keys > 0 && !d_count) || (n > 0 && !d_key)) return fail(ctx, KCC_EINVAL, "NULL key/count");
+  if (!aligned16(d_key)) return fail(ctx, KCC_EINVAL, "key must be 16-byte aligned");
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
   kcc::KeyedWork kw{};

@@ -816,9 +816,14 @@ __global__ __launch_bounds__(KB_GA_THREADS) void kb_gather(
     __syncthreads();
     if (c0 == 0) KCC_TLK(blockIdx.x, 1);
     // sub-batch t = segments [KB_GA_U2 t, KB_GA_U2 (t + 1)) of the chunk; wave wv takes
-    // t = wv, wv + KB_GA_WAVES, ...  Every load is issued whatever the segment's length (lanes
-    // past it re-read the segment's first record, a line the wave reads anyway), so each
-    // sub-batch issues the same instructions and the waits stay static
+    // t = wv, wv + KB_GA_WAVES, ...  Every load is issued whatever the segment's length, so
+    // each sub-batch issues the same instructions and the waits stay static: lanes past a
+    // segment's end re-read its first slot, a line the wave reads anyway.  An empty segment
+    // has no record of its own: its first slot is the next segment's first record or, past
+    // the tile's last used bucket, slot nvalid of the tile's region — for a full tile
+    // (nvalid = KB_SW_TILE) the next tile's first slot, and for a full last tile the slot
+    // sr[G * KB_SW_TILE] just past every region, which keyed_sr_slots' one-line pad keeps
+    // inside the allocation.  The value is read and never summed (o < len fails)
     const int nsb = (ch + KB_GA_U2 - 1) / KB_GA_U2;
     uint64_t ra[KB_GA_U2][2], rb[KB_GA_U2][2];
     uint32_t la[KB_GA_U2], fa[KB_GA_U2], lb[KB_GA_U2], fb[KB_GA_U2];
@@ -1032,9 +1037,14 @@ int64_t keyed_counts_words(int64_t n_keys, int64_t n) {
   const int64_t b = (nb / KB_TB + 1) * keyed_sweep_tiles(n) * KB_TB / 2;  // (u16 entries, blocked)
   return a > b ? a : b;
 }
+// One 128-byte line (KB_SR_PAD slots) past the last tile's region: kb_gather loads the
+// first slot of every segment, empty ones included, and an empty segment of a full last
+// tile (n a multiple of KB_SW_TILE, every key valid) starts at the region's end,
+// sr[tiles * KB_SW_TILE].
+constexpr int64_t KB_SR_PAD = 16;
 int64_t keyed_sr_slots(int64_t n) {
   const int64_t t = keyed_sweep_tiles(n) * KB_SW_TILE;
-  return t > n ? t : n;
+  return (t > n ? t : n) + KB_SR_PAD;
 }
 int64_t keyed_part_words(int64_t n_keys, int na) {  // (bucket groups x parts x arrays x rows)
   const int64_t ng = (keyed_buckets(n_keys) + KB_GA_BPG - 1) / KB_GA_BPG;

@@ -192,10 +192,22 @@ class CapacityEngine:
         return count
 
     def reduce_requests_keyed_async(self, n_keys, key, cpu_req, mem_req, used_cpu, used_mem,
-                                    stream=None):
+                                    stream=None, cpu_lim=None, mem_lim=None, lim_cpu=None,
+                                    lim_mem=None, n=None):
+        """Device form of get_pod_cpu_memory_requests_limits_keyed (torch tensors on the
+        engine's device, 16-byte aligned; outputs of n_keys elements, every row written).
+        The arguments go to the C-ABI as they are (None: NULL), which validates them; n:
+        the container count when it is not key.numel()."""
+        n = (0 if key is None else key.numel()) if n is None else n
         self._check(self._lib.kcc_reduce_requests_keyed_async(
-            self._h, n_keys, key.numel(), _dp(key), _dp(cpu_req), _dp(mem_req), None, None,
-            _dp(used_cpu), _dp(used_mem), None, None, _stream(stream)))
+            self._h, n_keys, n, _dp(key), _dp(cpu_req), _dp(mem_req), _dp(cpu_lim), _dp(mem_lim),
+            _dp(used_cpu), _dp(used_mem), _dp(lim_cpu), _dp(lim_mem), _stream(stream)))
+
+    def count_by_key_async(self, n_keys, key, count, stream=None, n=None):
+        """Device form of count_by_key: count[0:n_keys] (int64) = pods per row."""
+        n = (0 if key is None else key.numel()) if n is None else n
+        self._check(self._lib.kcc_count_by_key_async(
+            self._h, n_keys, n, _dp(key), _dp(count), _stream(stream)))
 
     def pod_requests_async(self, pod_ptr, cpu_req, mem_req, pod_cpu, pod_mem, init_ptr=None,
                            init_cpu=None, init_mem=None, restartable=None, ovh_cpu=None,

@@ -11,7 +11,10 @@
     s_setreg writes each), and the compiler inserts no mode switch of its own;
   - f32 and f64 denormals are enabled in the kernel descriptor (class A reads
     integers as denormals);
-  - no kernel spills to scratch.
+  - no kernel spills to scratch;
+  - the hand-offs without release / acquire — node prep reading the reduce's node sums
+    (kcc_kernels.hip) and the keyed gather's parts (kcc_keyed.hip kb_gather) — keep their
+    agent-scope (sc1) stores and loads and the vmcnt(0) drain before the flag / count.
 """
 import os
 import re
@@ -264,8 +267,8 @@ NPM = "reduce_kernelILi2ELb1E"
 VMEM = ("global_", "buffer_", "flat_")
 
 
-def _src_lines(pattern, within=None):
-    src = open(SRC).read().splitlines()
+def _src_lines(pattern, within=None, src=SRC):
+    src = open(src).read().splitlines()
     lo, hi = within if within else (0, len(src))
     if within:  # (function names -> the lines from its definition to the next top-level `}`)
         lo = next(i for i, ln in enumerate(src) if re.search(within[0], ln))
@@ -273,10 +276,10 @@ def _src_lines(pattern, within=None):
     return {i + 1 for i in range(lo, hi) if re.search(pattern, src[i])}
 
 
-def _asm_with_lines(tmp_path_factory, *defines):
+def _asm_with_lines(tmp_path_factory, *defines, src=SRC):
     out = tmp_path_factory.mktemp("isa_g") / "kcc_g.s"
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S",
-                    "--cuda-device-only", "-gline-tables-only", *defines, SRC, "-o", str(out)],
+                    "--cuda-device-only", "-gline-tables-only", *defines, src, "-o", str(out)],
                    check=True, capture_output=True)
     return out.read_text()
 
@@ -292,14 +295,14 @@ def _function(asm, name):
     return asm[m.end():asm.index(".Lfunc_end", m.end())]
 
 
-def _kernels_file_ids(asm):
-    """The .file numbers of kcc_kernels.hip in a line-table build."""
+def _kernels_file_ids(asm, name="kcc_kernels.hip"):
+    """The .file numbers of a source file (kcc_kernels.hip) in a line-table build."""
     return {int(m.group(1)) for m in
-            re.finditer(r'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"[^"]*kcc_kernels\.hip"', asm, re.M)}
+            re.finditer(rf'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"[^"]*{re.escape(name)}"', asm, re.M)}
 
 
 def _instrs_with_lines(body, fids=frozenset()):
-    """[(source line in kcc_kernels.hip or None, instruction text)] in program order."""
+    """[(source line in the files `fids` or None, instruction text)] in program order."""
     out, cur = [], None
     for ln in body.splitlines():
         s = ln.strip()
@@ -378,3 +381,123 @@ def test_npm_hand_off_check_catches_plain_stores(tmp_path_factory):
     bad = _asm_with_lines(tmp_path_factory, "-DKCC_VARIANT_BUILD", "-DKCC_DIAG_NP_NOSC1")
     problems = npm_ordering_problems(bad)
     assert any("node-sum store without sc1" in p for p in problems), problems
+
+
+# ---- kb_gather's part hand-off (kcc_keyed.hip) ------------------------------
+# Several workgroups ("parts") sum one bucket group.  Every part but the last to arrive
+# publishes its LDS rows to part_acc and raises the group's ready count; the last polls that
+# count, then adds the others' rows.  As in the reduce above there is no release / acquire:
+# (1) the part_acc stores are agent-scope (sc1), (2) each wave drains them (s_waitcnt
+# vmcnt(0)) before the barrier that precedes the ready add, (3) the ready poll and the
+# part_acc loads are agent-scope (sc1).
+KEYED_SRC = os.path.join(os.path.dirname(SRC), "kcc_keyed.hip")
+GATHERS = ("kb_gatherILi0E", "kb_gatherILi2E")
+# the publishing store: the product's agent-scope atomic store, or a plain one (the negative
+# control's textual replacement)
+GA_STORE = r"__hip_atomic_store\(mine \+|^\s*mine\[a \* KB_GA_ROWS \+ r\] ="
+GA_PLAIN_STORE = "mine[a * KB_GA_ROWS + r] = (uint64_t)acc[a][r];"
+
+
+@pytest.fixture(scope="module")
+def asm_keyed(tmp_path_factory):
+    out = tmp_path_factory.mktemp("isa_keyed") / "kcc_keyed.s"
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S",
+                    "--cuda-device-only", KEYED_SRC, "-o", str(out)], check=True,
+                   capture_output=True)
+    return out.read_text()
+
+
+@pytest.fixture(scope="module")
+def asm_keyed_g(tmp_path_factory):
+    return _asm_with_lines(tmp_path_factory, src=KEYED_SRC)
+
+
+def gather_hand_off_problems(asm_g, name, src=KEYED_SRC):
+    """What breaks the part hand-off in one kb_gather instantiation's ISA (empty: none);
+    asm_g: a line-table build of `src`, a file named kcc_keyed.hip."""
+    fids = _kernels_file_ids(asm_g, "kcc_keyed.hip")
+    assert fids, "no .file entry for kcc_keyed.hip"
+    ins = _instrs_with_lines(_function(asm_g, name), fids)
+    ga = (r"void kb_gather\(", None)
+    nacc = 2 if name.endswith("2E") else 1
+    problems = []
+    # (1) the part_acc stores: KB_GA_ROWS / KB_GA_THREADS = 8 rows per thread and array
+    # (the statement's line and the lines of the publishing block above it: the compiler
+    # may attribute a plain store to the line that forms `mine`)
+    stmt = _src_lines(GA_STORE, ga, src)
+    mine = _src_lines(r"uint64_t\* mine = part_acc \+", ga, src)
+    assert len(stmt) == 1 and len(mine) == 1 and min(mine) < min(stmt), (stmt, mine)
+    store_lines = set(range(min(mine), min(stmt) + 1))
+    stores = [i for i, (l, s) in enumerate(ins)
+              if l in store_lines and s.startswith(VMEM) and "store" in s]
+    if len(stores) < 8 * nacc:
+        problems.append(f"part_acc stores not found: {[ins[i][1] for i in stores]}")
+    problems += [f"part_acc store without sc1 (line {ins[i][0]}): {ins[i][1]}" for i in stores
+                 if not (ins[i][1].startswith("global_store_dwordx2 ") and
+                         ins[i][1].endswith("sc1"))]
+    # (2) last store ... s_waitcnt vmcnt(0) ... (no vector memory) ... s_barrier ... ready add
+    add_lines = _src_lines(r"__hip_atomic_fetch_add\(ready \+ b", ga, src)
+    adds = [i for i, (l, s) in enumerate(ins) if l in add_lines and s.startswith(VMEM)]
+    if len(adds) != 1 or not ins[adds[0]][1].startswith("global_atomic_add "):
+        problems.append(f"the ready add is not one global_atomic_add: {[ins[i][1] for i in adds]}")
+    elif stores:
+        last, add = stores[-1], adds[0]
+        bars = [i for i in range(last + 1, add) if ins[i][1].startswith("s_barrier")]
+        if last > add or not bars:
+            problems.append("no barrier between the last part_acc store and the ready add")
+        else:
+            bar = bars[-1]  # the barrier before the ready add
+            waits = [i for i in range(last + 1, bar)
+                     if ins[i][1].startswith("s_waitcnt") and "vmcnt(0)" in ins[i][1]]
+            if not waits:
+                problems.append("no s_waitcnt vmcnt(0) between the last part_acc store and "
+                                "the barrier before the ready add")
+            else:
+                problems += [f"vector memory access `{ins[i][1]}` between the vmcnt(0) and the "
+                             "barrier before the ready add"
+                             for i in range(waits[-1] + 1, bar) if ins[i][1].startswith(VMEM)]
+    # (3) the last part: the ready poll and the others' rows, agent-scope loads
+    poll_lines = _src_lines(r"__hip_atomic_load\(ready \+ b", ga, src)
+    polls = [s for l, s in ins if l in poll_lines and s.startswith(VMEM) and "load" in s]
+    if not polls:
+        problems.append("the ready poll's loads were not found")
+    problems += [f"ready poll without sc1: {s}" for s in polls
+                 if not (s.startswith("global_load_dword ") and s.endswith("sc1"))]
+    row_lines = _src_lines(r"__hip_atomic_load\(src \+ a \* KB_GA_ROWS \+", ga, src)
+    loads = [s for l, s in ins if l in row_lines and s.startswith(VMEM) and "load" in s]
+    if len(loads) < 8 * nacc:
+        problems.append(f"part_acc loads not found: {loads}")
+    problems += [f"part_acc load without sc1: {s}" for s in loads
+                 if not (s.startswith("global_load_dwordx2 ") and s.endswith("sc1"))]
+    return problems
+
+
+@pytest.mark.parametrize("name", GATHERS)
+def test_gather_line_tables_same_instructions(asm_keyed, asm_keyed_g, name):
+    """The line-table build of kcc_keyed.hip used below has exactly the release instructions."""
+    strip = lambda b: [s for _, s in _instrs_with_lines(b)]  # noqa: E731
+    assert strip(_function(asm_keyed, name)) == strip(_function(asm_keyed_g, name))
+
+
+@pytest.mark.parametrize("name", GATHERS)
+def test_gather_part_hand_off(asm_keyed_g, name):
+    """kb_gather<0> and kb_gather<2>: every part_acc store is a 64-bit sc1
+    store, an s_waitcnt vmcnt(0) with no vector memory access after it stands between the
+    last of them and the barrier before the ready add, and the ready poll and the part_acc
+    loads are sc1."""
+    assert gather_hand_off_problems(asm_keyed_g, name) == []
+
+
+def test_gather_hand_off_check_catches_plain_stores(tmp_path_factory):
+    """The check above fails on a copy of kcc_keyed.hip whose part_acc store statement is
+    replaced by a plain store: it reads the ISA, not the source."""
+    text = open(KEYED_SRC).read()
+    bad, n = re.subn(r"__hip_atomic_store\(mine \+ a \* KB_GA_ROWS \+ r,[^;]*;", GA_PLAIN_STORE,
+                     text)
+    assert n == 1, "the part_acc store statement was not found"
+    src = tmp_path_factory.mktemp("isa_keyed_bad") / "kcc_keyed.hip"
+    src.write_text(bad)
+    asm_bad = _asm_with_lines(tmp_path_factory, "-I" + os.path.dirname(KEYED_SRC), src=str(src))
+    for name in GATHERS:
+        problems = gather_hand_off_problems(asm_bad, name, str(src))
+        assert any("part_acc store without sc1" in p for p in problems), problems
