@@ -5,7 +5,8 @@
 // (-cluster) instead of client-go, and the two hot loops (CC:262-294, CC:105-140) run
 // on the GPU through the C-ABI (kcc_capacity).  Additions: -specs <file> (a batch of
 // what-if specs, one "cpuRequests memRequests replicas" per line), -v (per-node
-// report of CC:107-117/137), -device/-gpus.
+// report of CC:107-117/137), -device/-gpus, -byPool (the totals per node pool, from
+// kcc_fit_grouped: "Pool <name> : <total>" lines after the reference's output).
 #include <cctype>
 #include <cerrno>
 #include <cinttypes>
@@ -37,7 +38,8 @@ struct Flags {
       {"kubeconfig", ""},         {"cluster", ""},          {"cpuRequests", "100m"},
       {"cpuLimits", "200m"},      {"memRequests", "100mb"}, {"memLimits", "200mb"},
       {"replicas", "1"},          {"specs", ""},            {"device", "0"},
-      {"gpus", "1"},              {"v", "false"},           {"schedulerRequests", "false"}};
+      {"gpus", "1"},              {"v", "false"},           {"schedulerRequests", "false"},
+      {"byPool", "false"}};
 };
 
 // Go flag package syntax: -name=value, -name value, --name=value; bool -v.
@@ -61,7 +63,7 @@ bool parseFlags(int argc, char** argv, Flags& f) {
       std::fprintf(stderr, "flag provided but not defined: -%s\n", name.c_str());
       return false;
     }
-    if ((name == "v" || name == "schedulerRequests") && !has) {
+    if ((name == "v" || name == "schedulerRequests" || name == "byPool") && !has) {
       val = "true";
     } else if (!has) {
       if (i + 1 >= argc) {
@@ -133,6 +135,8 @@ int main(int argc, char** argv) {
   // opt-in (NOT the reference's semantics): pod requests as the
   // scheduler counts them — init containers, sidecars, overhead
   const bool schedReq = f.v["schedulerRequests"] == "true";
+  // the totals per node pool (the cluster file's `pool` lines) after the reference's output
+  const bool byPool = f.v["byPool"] == "true";
 
   Spec one{f.v["cpuRequests"], f.v["memRequests"], f.v["replicas"]};
   const uint64_t cpuLimits = convertCPUToMilis(f.v["cpuLimits"]);            // CC:65
@@ -265,6 +269,50 @@ int main(int argc, char** argv) {
                       in.pod_count.data(), (int64_t)specs.size(), sc.data(), sm.data(),
                       totals.data(), serr.data());
   if (rc) return fail(ctx, rc);
+
+  // -byPool: row i is in the pool of node i (an unhealthy node's zero row stays in its
+  // node's pool); pools in first-appearance order; ptot / perr [pool][spec]
+  std::vector<std::string> pools;
+  std::vector<int64_t> ptot;
+  std::vector<int32_t> perr;
+  if (byPool && n > 0) {
+    std::map<std::string, int32_t> id;
+    std::vector<int32_t> group((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      const std::string& name = cl.nodes[(size_t)i].pool;
+      auto it = id.find(name);
+      if (it == id.end()) {
+        it = id.emplace(name, (int32_t)pools.size()).first;
+        pools.push_back(name);
+      }
+      group[(size_t)i] = it->second;
+    }
+    std::vector<uint64_t> uc(suc);
+    std::vector<int64_t> um(sum_);
+    if (!schedReq) {  // the per-node request sums (CC:290-293) the grouped fit takes
+      uc.resize((size_t)n);
+      um.resize((size_t)n);
+      rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(),
+                               in.mem_req.data(), nullptr, nullptr, uc.data(), um.data(), nullptr,
+                               nullptr);
+      if (rc) return fail(ctx, rc);
+    }
+    ptot.resize(pools.size() * specs.size());
+    perr.resize(pools.size() * specs.size());
+    rc = kcc_fit_grouped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                         in.pod_count.data(), uc.data(), um.data(), group.data(),
+                         (int64_t)pools.size(), (int64_t)specs.size(), sc.data(), sm.data(),
+                         ptot.data(), perr.data());
+    if (rc) return fail(ctx, rc);
+  }
+  auto printPools = [&](size_t s) {
+    for (size_t g = 0; g < pools.size(); ++g) {
+      if (perr[g * specs.size() + s])
+        std::printf("Pool %s : panic: runtime error: integer divide by zero\n", pools[g].c_str());
+      else
+        std::printf("Pool %s : %" PRId64 "\n", pools[g].c_str(), ptot[g * specs.size() + s]);
+    }
+  };
   kcc_destroy(ctx);
 
   if (f.v["specs"].empty()) {  // CC:142-149, verbatim text
@@ -283,6 +331,7 @@ int main(int argc, char** argv) {
                   " replicas. Please try again by reducing the number of replicas or/and cpu/memory "
                   "resource requests. Exiting!!\n\n", specs[0].replicas);
     std::printf("%s\n", kRule);
+    printPools(0);
     return 0;
   }
   // batch: one line per spec
@@ -293,6 +342,7 @@ int main(int argc, char** argv) {
     else
       std::printf("%s %s %s total=%" PRId64 " %s\n", specs[s].cpuStr.c_str(), specs[s].memStr.c_str(),
                   specs[s].repStr.c_str(), totals[s], totals[s] >= specs[s].replicas ? "yes" : "no");
+    printPools(s);  // (-byPool: this spec's pools under its line)
   }
   return 0;
 }

@@ -120,6 +120,9 @@ bool loadCluster(const std::string& path, Cluster& out, std::string& err) {
       while (is >> c) n.conditions.push_back(c);
       if (n.conditions.size() < 4) return bad("a node needs 4 condition statuses (CC:212-213)");
       out.nodes.push_back(n);
+    } else if (kind == "pool") {
+      if (out.nodes.empty()) return bad("pool before any node");
+      if (!(is >> out.nodes.back().pool)) return bad("pool <name>");
     } else if (kind == "pod") {
       Pod p;
       if (!(is >> p.nodeName >> p.ns >> p.name >> p.phase)) return bad("pod <node|-> <ns> <name> <phase>");

@@ -55,6 +55,7 @@ struct NodeObj {
   std::string name, cpu, memory;  // Status.Allocatable cpu / memory (Quantity.String())
   int64_t pods = 0;               // Status.Allocatable.Pods().Value()
   std::vector<std::string> conditions;  // Status.Conditions[j].Status
+  std::string pool = "-";               // opaque node-pool name (`pool` line; "-": none given)
 };
 
 struct Cluster {
@@ -64,12 +65,13 @@ struct Cluster {
 
 // Cluster description file (one object per line, '#' comments):
 //   node <name> <cpu> <memory> <pods> <cond0> <cond1> <cond2> <cond3>
+//   pool <name>                       (of the last node; a node without one is in pool "-")
 //   pod <nodeName|-> <namespace> <name> <phase> [missing]
 //   container <cpuRequest> <cpuLimit> <memRequestBytes> <memLimitBytes>   (of the last pod)
 //   initcontainer <cpuRequest> <cpuLimit> <memRequestBytes> <memLimitBytes> [always]
 //   overhead <cpuMillis> <memBytes>                                         (of the last pod)
 // (init containers and overhead are read only by -schedulerRequests; the
-// reference's sums ignore them, CC:277.)
+// reference's sums ignore them, CC:277; the pool name is read only by -byPool.)
 // "-" as nodeName means "" (an unscheduled pod).  Returns false with a message on error.
 bool loadCluster(const std::string& path, Cluster& out, std::string& err);
 

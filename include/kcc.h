@@ -423,6 +423,45 @@ int kcc_fit_rows(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
                  int64_t spec_mem, int64_t* q, int32_t* row_err);
 
 /* ---------------------------------------------------------------------------
+ * Grouped fit: the totals of (b) broken down by node group, for S specs and G groups in one
+ * call.  The reference notes that its node loop "needs be modified depending what label
+ * selectors are applied to masters/nodes" (CC:188-194): a pod with a nodeSelector, node
+ * affinity or missing tolerations fits only some pools, and its answer is the sum of the
+ * eligible groups' cells.  group[i] (int32) is the group of node row i.
+ *   totals[g * S + s] = what kcc_fit returns for spec s on exactly the rows with
+ *     group[i] == g: CC:105-140 run on that sub-cluster, bit for bit — uint64 / int64 wrap,
+ *     int(uint64) reinterpretation (CC:119-124), truncating signed memory division with
+ *     MinInt64 / -1 == MinInt64 (CC:125-130), signed findMin (CC:133, CC:159-164), the
+ *     allocatablePods - len(pods) clamp (CC:134-136), the wrapping total (CC:138).
+ *   spec_err[g * S + s] = KCC_SPEC_DIVZERO iff Go would panic on that sub-cluster: some row
+ *     of g has free CPU and spec_cpu[s] == 0, or free memory and spec_mem[s] == 0; totals is
+ *     then 0 for that cell only.  A group made only of full rows does not panic on a zero
+ *     request.
+ *   Rows with group[i] < 0 or >= n_groups are skipped (as kcc_reduce_requests_keyed skips
+ *   keys); an empty group gives total 0, err 0; the ids need not be sorted.
+ *   For a spec with no flagged cell, the wrapping sum of its cells over the groups equals
+ *   kcc_fit on the rows that were not skipped.
+ * 1 <= n_groups, n_groups * n_specs <= 2^28, n_nodes <= 2^31 - 4096 (else KCC_EINVAL);
+ * n_nodes == 0 or n_specs == 0: KCC_OK, every output 0.  The host-array form runs on the
+ * context's device 0 and retains no caller pointer; the async form takes device pointers,
+ * only enqueues on `stream`, allocates only when a size exceeds every earlier call's and
+ * never synchronises.  No kernel of it waits on another workgroup: it cannot set a fault
+ * word, and it does not read them.
+ * ------------------------------------------------------------------------- */
+int kcc_fit_grouped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                    const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
+                    const uint64_t* used_cpu, const int64_t* used_mem, const int32_t* group,
+                    int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
+                    const int64_t* spec_mem, int64_t* totals /* [G * S] */,
+                    int32_t* spec_err /* [G * S] */);
+int kcc_fit_grouped_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                          const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
+                          const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                          const int64_t* d_used_mem, const int32_t* d_group, int64_t n_groups,
+                          int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                          int64_t* d_totals, int32_t* d_spec_err, void* stream);
+
+/* ---------------------------------------------------------------------------
  * OPT-IN scheduler request model — explicitly NOT the
  * reference's semantics: the reference sums only the app containers of a node's pods
  * (CC:276-294, kcc_reduce_requests above; that stays the default).  This gives the

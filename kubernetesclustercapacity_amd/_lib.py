@@ -82,6 +82,8 @@ SIGNATURES = {
     "kcc_count_by_key": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "kcc_count_by_key_async": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "kcc_fit_rows": (_int, [_vp, _i64] + [_vp] * 6 + [C.c_uint64, _i64, _vp, _vp]),
+    "kcc_fit_grouped": (_int, [_vp, _i64] + [_vp] * 7 + [_i64, _i64] + [_vp] * 4),
+    "kcc_fit_grouped_async": (_int, [_vp, _i64] + [_vp] * 7 + [_i64, _i64] + [_vp] * 5),
     "kcc_pod_requests": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 11),
     "kcc_pod_requests_async": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 12),
     "kcc_reduce_requests_pods": (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 12),

@@ -568,6 +568,45 @@ hipError_t launch_fit_rows(int64_t n, const uint64_t* alloc_cpu, const int64_t* 
                            const uint64_t* used_cpu, const int64_t* used_mem, uint64_t spec_cpu,
                            int64_t spec_mem, int64_t* q, int32_t* err, hipStream_t s);
 
+// ---- grouped fit: per node-group x spec totals (kcc_groups.hip) ------
+// The record of one node row, placed in group order: the exact path's integers (fc / fm
+// are 0 where the reference's `alloc <= used` branch divides nothing) and, for a fast row
+// (fc < 2^31, 0 <= fm < 2^50), the same two values as f64 (0.0 otherwise).
+struct __attribute__((aligned(16))) GrpRow {
+  uint64_t fc;
+  int64_t fm;
+  int64_t P;
+  int64_t cl;   // allocatable pods - pod count (wraps), CC:135
+  double fcd;
+  double fmd;
+};
+static_assert(sizeof(GrpRow) == 48, "GrpRow must be 48 B");
+// R: group-ordered rows one pair-loop workgroup walks (tests/test_groups.py restates it).
+// A wave flushes 64 x 8 B of atomics per run and group change, 8 S (N / R + G) bytes a call
+// (twice that for the cells that count a divide by zero): at 1M rows x 4096 specs x 1024
+// groups 162 MB, for 4.1e9 pairs.
+constexpr int GRP_RUN = 256;
+constexpr int GRP_PAIR_THREADS = 256;  // 4 waves x 64 specs per pair-loop workgroup
+constexpr int GRP_LDS_GROUPS = 4096;   // up to this G the sort's per-workgroup counts live in LDS
+constexpr int64_t GRP_MAX_CELLS = (int64_t)1 << 28;  // G x S
+constexpr int64_t GRP_MAX_NODES = ((int64_t)1 << 31) - 4096;
+inline int64_t grp_runs(int64_t n_nodes) { return (n_nodes + GRP_RUN - 1) / GRP_RUN; }
+struct GrpWork {
+  uint32_t* count;   // [G] rows per group
+  uint32_t* cursor;  // [G] next free slot of each group (starts at the exclusive scan)
+  uint32_t* total;   // [1] rows with a valid group id
+  GrpRow* rec;       // [n] records in group order
+  int32_t* rg;       // [n] the record's group | fast-row bit
+  int64_t* acc;      // [2 G S] the pre-finalize pair: wrapping sums, then divide-by-zero counts
+};
+// Every cell of totals / spec_err [G * S] is written.  n, G, S >= 1, G * S <= GRP_MAX_CELLS.
+hipError_t launch_fit_grouped(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+                              const int64_t* alloc_pods, const int64_t* pod_count,
+                              const uint64_t* used_cpu, const int64_t* used_mem,
+                              const int32_t* group, int64_t G, int64_t S, const uint64_t* spec_cpu,
+                              const int64_t* spec_mem, const GrpWork& w, int64_t* totals,
+                              int32_t* spec_err, hipStream_t s);
+
 // ---- opt-in scheduler request model (kcc_pods.hip) ---------------
 hipError_t launch_pod_requests(int64_t n_pods, int64_t n_cont, int64_t n_init,
                                const int64_t* pod_ptr, const uint64_t* cpu_req,

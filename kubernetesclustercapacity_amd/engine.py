@@ -140,6 +140,40 @@ class CapacityEngine:
                                       _p(totals), _p(err)))
         return totals, err
 
+    def fit_grouped(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                    group, n_groups, spec_cpu, spec_mem):
+        """CC:101-140 per node group: totals[g, s] is total_possible_max_replicas on the rows
+        with group[i] == g (ids < 0 or >= n_groups: skipped), err[g, s] = 1 where Go would
+        panic on that sub-cluster.  Returns (totals int64[G, S], err int32[G, S]); a
+        selector's answer is select_groups over its eligible groups."""
+        a = [_arr(alloc_cpu, np.uint64), _arr(alloc_mem, np.int64), _arr(alloc_pods, np.int64),
+             _arr(pod_count, np.int64), _arr(used_cpu, np.uint64), _arr(used_mem, np.int64)]
+        n = a[0].size
+        group = _key32(group)
+        if any(x.size != n for x in a) or group.size != n:
+            raise ValueError("node arrays differ in length")
+        sc, sm = _arr(spec_cpu, np.uint64), _arr(spec_mem, np.int64)
+        if sc.size != sm.size:
+            raise ValueError("spec arrays differ in length")
+        G = int(n_groups)
+        totals = np.zeros((max(G, 0), sc.size), np.int64)
+        err = np.zeros((max(G, 0), sc.size), np.int32)
+        self._check(self._lib.kcc_fit_grouped(self._h, n, *[_p(x) for x in a], _p(group), G,
+                                              sc.size, _p(sc), _p(sm), _p(totals), _p(err)))
+        return totals, err
+
+    def fit_grouped_async(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                          group, n_groups, spec_cpu, spec_mem, totals, spec_err, stream=None):
+        """Device form of fit_grouped (torch tensors on the engine's device; group int32,
+        totals int64 / spec_err int32 of n_groups * n_specs elements).  The arguments go to
+        the C-ABI as they are (None: NULL), which validates them."""
+        n = 0 if alloc_cpu is None else alloc_cpu.numel()
+        s = 0 if spec_cpu is None else spec_cpu.numel()
+        self._check(self._lib.kcc_fit_grouped_async(
+            self._h, n, _dp(alloc_cpu), _dp(alloc_mem), _dp(alloc_pods), _dp(pod_count),
+            _dp(used_cpu), _dp(used_mem), _dp(group), int(n_groups), s, _dp(spec_cpu),
+            _dp(spec_mem), _dp(totals), _dp(spec_err), _stream(stream)))
+
     def capacity(self, node_ptr, cpu_req, mem_req, alloc_cpu, alloc_mem, alloc_pods, pod_count,
                  spec_cpu, spec_mem):
         """Fused (a)+(b) on host arrays.  Returns (totals, spec_err)."""
@@ -520,6 +554,28 @@ def _stream(stream):
         return None
     h = getattr(stream, "cuda_stream", stream)
     return C.c_void_p(int(h)) if h else None
+
+
+def select_groups(totals, err, eligible):
+    """The reference run on the nodes of the eligible groups, from fit_grouped's cells (host
+    arithmetic on G x S numbers).  eligible: bool [G, S] (per spec) or [G].  Returns
+    (totals int64[S], err int32[S]): err[s] = 1 when an eligible cell of spec s is flagged
+    (Go would panic on that sub-cluster), totals[s] = the wrapping sum of the eligible
+    cells, 0 where err[s] is set."""
+    t = np.asarray(totals, np.int64)
+    e = np.asarray(err, np.int32)
+    if t.ndim != 2 or e.shape != t.shape:
+        raise ValueError("totals and err must both be [G, S]")
+    m = np.asarray(eligible, bool)
+    if m.shape == t.shape[:1]:
+        m = np.broadcast_to(m[:, None], t.shape)
+    if m.shape != t.shape:
+        raise ValueError("eligible must be [G, S] or [G]")
+    flagged = ((e != 0) & m).any(axis=0)
+    # uint64 addition wraps as Go's int64 does
+    s = np.where(m, t, 0).astype(np.int64).view(np.uint64).sum(axis=0, dtype=np.uint64)
+    out = np.where(flagged, np.uint64(0), s).astype(np.uint64).view(np.int64)
+    return out, flagged.astype(np.int32)
 
 
 def verdict(totals, replicas):

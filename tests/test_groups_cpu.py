@@ -1,0 +1,237 @@
+"""Grouped fit (kcc_fit_grouped), the checks that need no GPU:
+
+  - the header declares both entry points and _lib.SIGNATURES binds them with its arity;
+  - select_groups (host arithmetic on the G x S cells) against the C oracle run on the
+    union of the eligible groups' rows;
+  - a model of the pair loop's fast path (kcc_groups.hip grp_div), restated in numpy f64
+    and Python integers, against exact division on the stated bounds
+        fast row : free CPU < 2^31, 0 <= free memory < 2^50
+        fast spec: 1 <= c <= 2^52, 1 <= m <= 2^52
+    t = trunc(f * (1 / d)) is within 1 of floor(f / d) and the exact remainder
+    r = fma(-t, d, f) = f - t d tells which way (r < 0: t - 1; r >= d: t + 1);
+  - kcc_groups.hip compiles for gfx950 and no kernel of it uses private-segment (spill)
+    memory.
+"""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from kubernetesclustercapacity_amd import _lib, select_groups, synth
+from oracle import coracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "kubernetesclustercapacity_amd", "csrc", "kcc_groups.hip")
+U64 = 1 << 64
+
+FC_MAX = 1 << 31    # kcc_groups.hip GRP_FC_MAX
+FM_MAX = 1 << 50    # GRP_FM_MAX
+SPEC_MAX = 1 << 52  # GRP_SPEC_MAX
+
+
+# ---- ABI ---------------------------------------------------------------------------------
+def test_header_and_signatures():
+    ar = _lib.header_arities()
+    assert ar.get("kcc_fit_grouped") == 15
+    assert ar.get("kcc_fit_grouped_async") == 16
+    for name in ("kcc_fit_grouped", "kcc_fit_grouped_async"):
+        assert name in _lib.header_symbols()
+        assert len(_lib.SIGNATURES[name][1]) == ar[name]
+
+
+# ---- select_groups -----------------------------------------------------------------------
+def _wrap_i64(x):
+    x %= U64
+    return x - U64 if x >= 1 << 63 else x
+
+
+@pytest.fixture(scope="module")
+def cells():
+    """A 600-row adversarial cluster in G = 6 groups (group 5 empty) and 24 specs: the
+    per-group cells from the oracle run on each group's rows."""
+    n, G, S = 600, 6, 24
+    c = synth.make_cluster(n, 20 * n, seed=11, chunk=1024, adversarial=True)
+    uc, um, _, _ = coracle.reduce_requests(c.node_ptr, c.cpu_req, c.mem_req)
+    sc, sm = synth.make_specs(S, seed=11, adversarial=True)
+    rng = np.random.default_rng(11)
+    gid = rng.integers(0, G - 1, n).astype(np.int32)
+    # group 4: full rows only (no free CPU, no free memory) -> never flagged
+    full = gid == 4
+    c.alloc_cpu[full] = uc[full]
+    c.alloc_mem[full] = um[full]
+    rows = [c.alloc_cpu, c.alloc_mem, c.alloc_pods, c.pod_count, uc, um]
+    tot = np.zeros((G, S), np.int64)
+    err = np.zeros((G, S), np.int32)
+    for g in range(G):
+        sel = gid == g
+        tot[g], err[g] = coracle.fit(*[a[sel] for a in rows], sc, sm)
+    return rows, gid, sc, sm, tot, err
+
+
+def _union(rows, gid, sc, sm, mask_col, s):
+    sel = np.isin(gid, np.flatnonzero(mask_col))
+    t, e = coracle.fit(*[a[sel] for a in rows], sc[s:s + 1], sm[s:s + 1])
+    return int(t[0]), int(e[0])
+
+
+def test_select_groups_matches_oracle_on_union(cells):
+    rows, gid, sc, sm, tot, err = cells
+    G, S = tot.shape
+    assert err.any() and not err.all() and not err[4].any() and not err[5].any()
+    rng = np.random.default_rng(5)
+    masks = [rng.random((G, S)) < p for p in (0.5, 0.2, 0.9)]
+    masks += [np.zeros((G, S), bool), np.ones((G, S), bool)]
+    for m in masks:
+        t, e = select_groups(tot, err, m)
+        assert t.dtype == np.int64 and e.dtype == np.int32 and t.shape == e.shape == (S,)
+        for s in range(S):
+            ot, oe = _union(rows, gid, sc, sm, m[:, s], s)
+            assert int(e[s]) == oe, s
+            assert int(t[s]) == (0 if oe else ot), s
+    for m1 in ([True, False, True, False, True, False], [False] * 4 + [True, True]):
+        t, e = select_groups(tot, err, np.array(m1))
+        for s in range(S):
+            ot, oe = _union(rows, gid, sc, sm, np.array(m1), s)
+            assert (int(t[s]), int(e[s])) == ((0 if oe else ot), oe), s
+
+
+def test_select_groups_flag_follows_eligibility(cells):
+    rows, gid, sc, sm, tot, err = cells
+    G, S = tot.shape
+    s = int(np.flatnonzero(sc == 0)[0])  # cpu request 0: flagged wherever a row has free CPU
+    assert err[:4, s].all() and not err[4, s]
+    only_full = np.zeros((G, S), bool)
+    only_full[4] = True  # the spec's flagged cells are all ineligible
+    t, e = select_groups(tot, err, only_full)
+    assert int(e[s]) == 0 and int(t[s]) == int(tot[4, s])
+    with_flagged = only_full.copy()
+    with_flagged[2, s] = True  # one flagged cell eligible
+    t, e = select_groups(tot, err, with_flagged)
+    assert int(e[s]) == 1 and int(t[s]) == 0
+    # wrapping sum: two cells whose int64 sum overflows
+    big = np.array([[np.iinfo(np.int64).max], [5]], np.int64)
+    t, e = select_groups(big, np.zeros((2, 1), np.int32), [True, True])
+    assert int(t[0]) == _wrap_i64((1 << 63) - 1 + 5) and int(e[0]) == 0
+    with pytest.raises(ValueError):
+        select_groups(tot, err, np.ones((G + 1,), bool))
+
+
+# ---- the fast path's model ---------------------------------------------------------------
+def model_div(f, d, ulps=0):
+    """grp_div: floor(f / d) as the kernel's fast path computes it.  ulps: the reciprocal
+    moved that many f64 steps (the proof leaves room for a reciprocal 2 ulp off)."""
+    f = np.asarray(f, np.int64)
+    d = np.asarray(d, np.int64)
+    fd, dd = f.astype(np.float64), d.astype(np.float64)
+    assert (fd.astype(np.int64) == f).all() and (dd.astype(np.int64) == d).all()  # held exactly
+    rd = 1.0 / dd
+    for _ in range(abs(ulps)):
+        rd = np.nextafter(rd, np.inf if ulps > 0 else 0.0)
+    t = np.trunc(fd * rd).astype(np.int64)
+    r = f - t * d  # what fma(-t, d, f) returns: exact while |r| <= 2^53
+    assert (np.abs(r) <= 1 << 53).all()
+    t = t - (r < 0) + (r >= d)
+    return t
+
+
+def model_q(fc, fm, P, cl, c, m):
+    """One fast pair: findMin of the two quotients, converted through int32, clamped."""
+    q = np.minimum(model_div(fc, c), model_div(fm, m))
+    q = np.minimum(q, (1 << 31) - 1)  # v_cvt_i32_f64 saturates
+    return np.where(q >= P, cl, q)
+
+
+def _edge_values(lo, hi_excl, rng, k):
+    """k values of [lo, hi_excl): both edges, powers of two and their neighbours, random."""
+    v = [lo, lo + 1, hi_excl - 1, hi_excl - 2]
+    b = 1
+    while b < hi_excl:
+        v += [x for x in (b - 1, b, b + 1) if lo <= x < hi_excl]
+        b <<= 1
+    bits = rng.integers(1, int(hi_excl - 1).bit_length() + 1, k)
+    r = (rng.integers(0, 1 << 62, k) >> (62 - bits)).astype(np.int64)
+    return np.concatenate([np.array(v, np.int64), np.clip(r, lo, hi_excl - 1)])
+
+
+def test_fast_division_model_is_exact_on_the_bounds():
+    rng = np.random.default_rng(7)
+    pairs = 0
+    for fmax in (FC_MAX, FM_MAX):
+        f = _edge_values(0, fmax, rng, 600)
+        d = _edge_values(1, SPEC_MAX + 1, rng, 600)
+        F, D = [x.ravel() for x in np.meshgrid(f, d)]
+        # exact multiples and their neighbours, where a quotient off by one shows
+        k = rng.integers(0, 1 << 20, F.size)
+        mult = np.clip((F // np.maximum(D, 1)) * D + (k % 3 - 1), 0, fmax - 1)
+        for ff in (F, mult):
+            exact = ff // D  # non-negative int64: exact
+            for ulps in (0, 2, -2):
+                assert np.array_equal(model_div(ff, D, ulps), exact)
+            pairs += ff.size
+    assert pairs >= 100_000
+    # every corner of the four bounds, in Python integers
+    for fc in (0, FC_MAX - 1):
+        for fm in (0, FM_MAX - 1):
+            for c in (1, SPEC_MAX):
+                for m in (1, SPEC_MAX):
+                    q = int(model_q(np.array([fc]), np.array([fm]), np.array([1 << 40]),
+                                    np.array([-9]), np.array([c]), np.array([m]))[0])
+                    assert q == min(fc // c, fm // m)
+
+
+def test_fast_path_needs_its_cpu_bound():
+    """Free CPU 2^31, one step past the fast-row bound, with c = m = 1: the quotient 2^31
+    does not fit the int32 conversion of the fast path (it would give 2^31 - 1).  The row
+    pass sends such a row to the exact path."""
+    fc = np.array([FC_MAX])
+    got = int(model_q(fc, np.array([FM_MAX - 1]), np.array([1 << 40]), np.array([0]),
+                      np.array([1]), np.array([1]))[0])
+    assert got == FC_MAX - 1 != FC_MAX // 1
+    # free memory past 2^53 is not even held by an f64
+    assert int(np.float64((1 << 53) + 1)) != (1 << 53) + 1
+
+
+def test_fast_pair_clamp_model():
+    rng = np.random.default_rng(9)
+    n = 20_000
+    fc = rng.integers(0, FC_MAX, n)
+    fm = rng.integers(0, FM_MAX, n)
+    c = rng.integers(1, 8000, n)
+    m = rng.integers(1 << 20, 1 << 35, n)
+    P = rng.integers(-3, 300, n)
+    cl = P - rng.integers(0, 300, n)
+    q = np.minimum(fc // c, fm // m)
+    assert np.array_equal(model_q(fc, fm, P, cl, c, m), np.where(q >= P, cl, q))
+
+
+# ---- the kernels compile for gfx950 without spills ----------------------------------------
+HIPCC = shutil.which("hipcc") or shutil.which(
+    os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc"))
+
+KERNELS = ["grp_hist_kernel", "grp_scan_kernel", "grp_scatter_kernel", "grp_pairs_kernel",
+           "grp_finalize_kernel"]
+
+
+@pytest.mark.skipif(HIPCC is None, reason="hipcc not available")
+def test_kernels_compile_without_scratch(tmp_path):
+    out = tmp_path / "kcc_groups.s"
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S",
+                    "--cuda-device-only", "-I", os.path.join(ROOT, "include"), SRC, "-o",
+                    str(out)], check=True, capture_output=True)
+    asm = out.read_text()
+    meta = {}
+    for blk in asm.split("- .agpr_count")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
+                      for k in ("private_segment_fixed_size", "vgpr_count", "sgpr_count",
+                                "group_segment_fixed_size")}
+    for k in KERNELS:
+        hit = [v for name, v in meta.items() if k in name]
+        assert len(hit) == 1, (k, sorted(meta))
+        print(k, hit[0])
+        assert hit[0]["private_segment_fixed_size"] == 0, k
+    assert len(meta) == len(KERNELS)
+    assert set(re.findall(r"; ScratchSize: (\d+)", asm)) == {"0"}
