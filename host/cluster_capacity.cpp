@@ -6,7 +6,13 @@
 // on the GPU through the C-ABI (kcc_capacity).  Additions: -specs <file> (a batch of
 // what-if specs, one "cpuRequests memRequests replicas" per line), -v (per-node
 // report of CC:107-117/137), -device/-gpus, -byPool (the totals per node pool, from
-// kcc_fit_grouped: "Pool <name> : <total>" lines after the reference's output).
+// kcc_fit_grouped: "Pool <name> : <total>" lines after the reference's output),
+// -extRequests name=amount[,name=amount...] (the pod also requests extended resources —
+// device-plugin GPUs, ephemeral-storage, hugepages — which the cluster file gives per node
+// as `resource` lines and per container as `request` lines; in a -specs file trailing
+// name=amount columns say the same per spec.  Totals, pools and -v's "Max replicas" then
+// come from kcc_fit_ext; the output format does not change).
+#include <array>
 #include <cctype>
 #include <cerrno>
 #include <cinttypes>
@@ -39,7 +45,7 @@ struct Flags {
       {"cpuLimits", "200m"},      {"memRequests", "100mb"}, {"memLimits", "200mb"},
       {"replicas", "1"},          {"specs", ""},            {"device", "0"},
       {"gpus", "1"},              {"v", "false"},           {"schedulerRequests", "false"},
-      {"byPool", "false"}};
+      {"byPool", "false"},        {"extRequests", ""}};
 };
 
 // Go flag package syntax: -name=value, -name value, --name=value; bool -v.
@@ -77,11 +83,159 @@ bool parseFlags(int argc, char** argv, Flags& f) {
   return true;
 }
 
+using NameAmount = std::vector<std::pair<std::string, std::string>>;
+
 struct Spec {
   std::string cpuStr, memStr, repStr;
   uint64_t cpu = 0;
   int64_t mem = 0, replicas = 0;
+  NameAmount ext;  // requests of extended resources (Quantity strings)
 };
+
+// "name=amount[,name=amount...]"; false on an item that is not name=amount.
+bool parseExtList(const std::string& list, NameAmount& out) {
+  std::istringstream is(list);
+  std::string item;
+  while (std::getline(is, item, ',')) {
+    const size_t eq = item.find('=');
+    if (eq == std::string::npos || eq == 0 || eq + 1 == item.size()) return false;
+    out.emplace_back(item.substr(0, eq), item.substr(eq + 1));
+  }
+  return true;
+}
+
+// The spec lines of a -specs file as strings: "cpuRequests memRequests replicas" and any
+// trailing name=amount columns (other trailing tokens are ignored, a '#' token ends them).
+bool readSpecFile(const std::string& path, std::vector<Spec>& out) {
+  std::ifstream sf(path);
+  if (!sf) return false;
+  std::string line;
+  while (std::getline(sf, line)) {
+    std::istringstream is(line);
+    Spec s;
+    if (!(is >> s.cpuStr >> s.memStr >> s.repStr) || s.cpuStr[0] == '#') continue;
+    std::string tok;
+    while (is >> tok && tok[0] != '#') {
+      const size_t eq = tok.find('=');
+      if (eq != std::string::npos && eq != 0) s.ext.emplace_back(tok.substr(0, eq), tok.substr(eq + 1));
+    }
+    out.push_back(s);
+  }
+  return true;
+}
+
+// The extended resources of a run: the union of the names the specs request, in
+// first-appearance order, and every amount as Quantity.Value().
+struct ExtRun {
+  std::vector<std::string> names;
+  std::vector<int64_t> spec_x;   // [R * S]
+  std::vector<int64_t> alloc_x;  // [R * N]; a node without a `resource` line of a name: 0
+  std::vector<int64_t> used_x;   // [R * N]
+  std::map<const Container*, std::array<int64_t, KCC_EXT_MAX>> creq;  // per app container
+  int64_t R() const { return (int64_t)names.size(); }
+  int index(const std::string& name) const {
+    for (size_t r = 0; r < names.size(); ++r)
+      if (names[r] == name) return (int)r;
+    return -1;
+  }
+};
+
+// Names from the specs (more than KCC_EXT_MAX: an error), then every amount of the run —
+// the specs' requests, the nodes' `resource` lines, the containers' `request` lines of
+// those names — in one kcc_parse_quantity batch.  Returns false with a message.
+bool loadExt(kcc_ctx* ctx, const std::vector<Spec>& specs, const Cluster& cl, ExtRun& x,
+             std::string& err) {
+  for (const Spec& s : specs)
+    for (const auto& na : s.ext)
+      if (x.index(na.first) < 0) x.names.push_back(na.first);
+  if (x.R() > KCC_EXT_MAX) {
+    err = "too many extended resources: " + std::to_string(x.R()) + " names requested, at most " +
+          std::to_string(KCC_EXT_MAX);
+    return false;
+  }
+  const size_t R = (size_t)x.R(), S = specs.size(), N = cl.nodes.size();
+  x.spec_x.assign(R * S, 0);
+  x.alloc_x.assign(R * N, 0);
+  std::string chars;
+  std::vector<int64_t> off{0};
+  std::vector<int64_t*> dst;                       // where each parsed value goes
+  std::vector<std::pair<const std::string*, const std::string*>> what;  // (name, amount)
+  auto add = [&](const std::pair<std::string, std::string>& na, int64_t* to) {
+    chars += na.second;
+    off.push_back((int64_t)chars.size());
+    dst.push_back(to);
+    what.emplace_back(&na.first, &na.second);
+  };
+  for (size_t s = 0; s < S; ++s)
+    for (const auto& na : specs[s].ext) add(na, &x.spec_x[(size_t)x.index(na.first) * S + s]);
+  for (size_t i = 0; i < N; ++i)
+    for (const auto& na : cl.nodes[i].resources)
+      if (x.index(na.first) >= 0) add(na, &x.alloc_x[(size_t)x.index(na.first) * N + i]);
+  for (const Pod& p : cl.pods)
+    for (const Container& ct : p.containers) {
+      if (ct.init) continue;  // requests of init containers are not read
+      for (const auto& na : ct.requests)
+        if (x.index(na.first) >= 0) {
+          auto it = x.creq.emplace(&ct, std::array<int64_t, KCC_EXT_MAX>{}).first;
+          add(na, &it->second[(size_t)x.index(na.first)]);
+        }
+    }
+  const int64_t ns = (int64_t)dst.size();
+  std::vector<int64_t> val((size_t)ns);
+  std::vector<int8_t> st((size_t)ns);
+  chars.resize((chars.size() + 4) & ~(size_t)3, '\0');  // 4-byte padded buffer
+  if (ns > 0) {
+    const int rc = kcc_parse_quantity(ctx, ns, chars.data(), off[(size_t)ns], off.data(), val.data(),
+                                      st.data());
+    if (rc) {
+      err = std::string("kcc error ") + std::to_string(rc) + ": " + kcc_last_error(ctx);
+      return false;
+    }
+  }
+  for (int64_t k = 0; k < ns; ++k) {
+    if (st[(size_t)k] != KCC_PARSE_OK) {
+      err = "invalid quantity \"" + *what[(size_t)k].second + "\" for resource " +
+            *what[(size_t)k].first;
+      return false;
+    }
+    *dst[(size_t)k] = val[(size_t)k];
+  }
+  return true;
+}
+
+// Per-node sums of the containers' requests of each resource (the memory column's wrapping
+// int64 sum, CC:291/293) through kcc_reduce_requests: a resource's per-container column
+// rides in an int64 slot (mem_req / mem_lim), two resources per call.  Unhealthy nodes' zero
+// rows get 0 allocatable.
+int sumExt(kcc_ctx* ctx, const std::vector<node>& rows, const EngineInputs& in, ExtRun& x) {
+  const size_t R = (size_t)x.R(), n = rows.size(), nc = in.app.size();
+  for (size_t i = 0; i < n; ++i)
+    if (rows[i].name.empty())
+      for (size_t r = 0; r < R; ++r) x.alloc_x[r * n + i] = 0;
+  x.used_x.assign(R * n, 0);
+  if (n == 0 || nc == 0) return KCC_OK;
+  std::vector<uint64_t> cpu_out(n), cpu_out2(n);
+  std::vector<int64_t> col[2], out[2];
+  for (size_t r0 = 0; r0 < R; r0 += 2) {
+    for (size_t j = 0; j < 2; ++j) {
+      col[j].assign(nc, 0);
+      out[j].assign(n, 0);
+      if (r0 + j >= R) continue;
+      for (size_t k = 0; k < nc; ++k) {
+        const auto it = x.creq.find(in.app[k]);
+        if (it != x.creq.end()) col[j][k] = it->second[r0 + j];
+      }
+    }
+    const int rc = kcc_reduce_requests(ctx, (int64_t)n, (int64_t)nc, in.node_ptr.data(),
+                                       in.cpu_req.data(), col[0].data(), in.cpu_lim.data(),
+                                       col[1].data(), cpu_out.data(), out[0].data(),
+                                       cpu_out2.data(), out[1].data());
+    if (rc) return rc;
+    for (size_t j = 0; j < 2 && r0 + j < R; ++j)
+      std::copy(out[j].begin(), out[j].end(), x.used_x.begin() + (long)((r0 + j) * n));
+  }
+  return KCC_OK;
+}
 
 bool goAtoiStrict(const std::string& s, int64_t& out) {
   char* end = nullptr;
@@ -138,7 +292,44 @@ int main(int argc, char** argv) {
   // the totals per node pool (the cluster file's `pool` lines) after the reference's output
   const bool byPool = f.v["byPool"] == "true";
 
-  Spec one{f.v["cpuRequests"], f.v["memRequests"], f.v["replicas"]};
+  Spec one{f.v["cpuRequests"], f.v["memRequests"], f.v["replicas"], 0, 0, 0, {}};
+  if (!parseExtList(f.v["extRequests"], one.ext)) {
+    std::fprintf(stderr, "invalid value \"%s\" for flag -extRequests: want name=amount[,name=amount...]\n",
+                 f.v["extRequests"].c_str());
+    return 2;
+  }
+  // the spec lines as strings; they are parsed where the reference parses its flags (below)
+  std::vector<Spec> specs;
+  const bool specFileOk = f.v["specs"].empty() || readSpecFile(f.v["specs"], specs);
+  if (f.v["specs"].empty()) specs.push_back(one);
+
+  // Extended resources: when a spec names one, the cluster is loaded and every amount
+  // converted before anything is printed — a rejected quantity or a fifth name is a load
+  // error (stderr, exit status 1, nothing on stdout).
+  Cluster cl;
+  kcc_ctx* ctx = nullptr;
+  ExtRun ext;
+  bool useExt = false;
+  for (const Spec& s : specs) useExt = useExt || !s.ext.empty();
+  const std::string path = !f.v["cluster"].empty() ? f.v["cluster"] : f.v["kubeconfig"];
+  if (useExt) {
+    std::string err;
+    if (path.empty()) {
+      std::fprintf(stderr, "no cluster: pass -cluster <file> (client-go is not part of this build)\n");
+      return 1;
+    }
+    if (!loadCluster(path, cl, err)) {
+      std::fprintf(stderr, "panic: %s\n", err.c_str());
+      return 2;
+    }
+    const int rc = kcc_create(&ctx, std::atoi(f.v["device"].c_str()), std::atoi(f.v["gpus"].c_str()));
+    if (rc) return fail(nullptr, rc);
+    if (!loadExt(ctx, specs, cl, ext, err)) {
+      std::fprintf(stderr, "%s\n", err.c_str());
+      kcc_destroy(ctx);
+      return 1;
+    }
+  }
   const uint64_t cpuLimits = convertCPUToMilis(f.v["cpuLimits"]);            // CC:65
   parseSpec(one, true);                                                      // CC:64, 67-71, 79-83
   const auto memLim = ToBytes(f.v["memLimits"]);                             // CC:73-77
@@ -151,40 +342,31 @@ int main(int argc, char** argv) {
               "%" PRIu64 " %" PRIu64 " %" PRId64 " %" PRId64 " %" PRId64 "\n",
               cpuLimits, one.cpu, memLim.first, one.mem, one.replicas);  // CC:85
 
-  std::vector<Spec> specs;
   if (!f.v["specs"].empty()) {
-    std::ifstream sf(f.v["specs"]);
-    if (!sf) {
+    if (!specFileOk) {
       std::fprintf(stderr, "cannot open spec file %s\n", f.v["specs"].c_str());
       return 1;
     }
-    std::string line;
-    while (std::getline(sf, line)) {
-      std::istringstream is(line);
-      Spec s;
-      if (!(is >> s.cpuStr >> s.memStr >> s.repStr) || s.cpuStr[0] == '#') continue;
-      parseSpec(s, false);
-      specs.push_back(s);
-    }
+    for (Spec& s : specs) parseSpec(s, false);
   } else {
-    specs.push_back(one);
+    specs[0] = one;  // (parsed above, CC:64-83)
   }
 
   // cluster access (CC:88-99): a cluster file replaces kubeconfig + client-go
-  const std::string path = !f.v["cluster"].empty() ? f.v["cluster"] : f.v["kubeconfig"];
   if (path.empty()) {
     std::fprintf(stderr, "no cluster: pass -cluster <file> (client-go is not part of this build)\n");
     return 1;
   }
-  Cluster cl;
-  std::string err;
-  if (!loadCluster(path, cl, err)) {
-    std::fprintf(stderr, "panic: %s\n", err.c_str());
-    return 2;
+  int rc = 0;
+  if (!useExt) {  // (with extended resources: loaded and created above)
+    std::string err;
+    if (!loadCluster(path, cl, err)) {
+      std::fprintf(stderr, "panic: %s\n", err.c_str());
+      return 2;
+    }
+    rc = kcc_create(&ctx, std::atoi(f.v["device"].c_str()), std::atoi(f.v["gpus"].c_str()));
+    if (rc) return fail(nullptr, rc);
   }
-  kcc_ctx* ctx = nullptr;
-  int rc = kcc_create(&ctx, std::atoi(f.v["device"].c_str()), std::atoi(f.v["gpus"].c_str()));
-  if (rc) return fail(nullptr, rc);
   std::vector<node> rows;
   rc = getHealthyNodes(ctx, cl, rows);  // node cpu / memory strings parsed on the device
   if (rc) return fail(ctx, rc);
@@ -210,6 +392,22 @@ int main(int argc, char** argv) {
     if (rc) return fail(ctx, rc);
   }
 
+  // extended resources: the per-node sums of each, and the cpu / memory sums kcc_fit_ext takes
+  std::vector<uint64_t> euc(suc);
+  std::vector<int64_t> eum(sum_);
+  if (useExt) {
+    rc = sumExt(ctx, rows, in, ext);
+    if (rc) return fail(ctx, rc);
+    if (!schedReq) {
+      euc.assign((size_t)n, 0);
+      eum.assign((size_t)n, 0);
+      rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(), in.mem_req.data(),
+                               nullptr, nullptr, euc.data(), eum.data(), nullptr, nullptr);
+      if (rc) return fail(ctx, rc);
+    }
+  }
+  const int64_t S = (int64_t)specs.size();
+
   if (verbose) {  // CC:107-117, 137 — per-node sums and fit, one row at a time
     std::vector<uint64_t> uc(n), lc(n);
     std::vector<int64_t> um(n), lm(n);
@@ -224,9 +422,21 @@ int main(int argc, char** argv) {
     // every row's "Max replicas" (CC:137) for the first spec in one device call
     std::vector<int64_t> qs(n);
     std::vector<int32_t> es(n);
-    rc = kcc_fit_rows(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
-                      in.pod_count.data(), uc.data(), um.data(), specs[0].cpu, specs[0].mem,
-                      qs.data(), es.data());
+    if (useExt) {  // every row its own group: cell i is row i's q for the first spec
+      std::vector<int32_t> each((size_t)n);
+      for (int64_t i = 0; i < n; ++i) each[(size_t)i] = (int32_t)i;
+      std::vector<int64_t> x0((size_t)ext.R());
+      for (int64_t r = 0; r < ext.R(); ++r) x0[(size_t)r] = ext.spec_x[(size_t)(r * S)];
+      if (n > 0)
+        rc = kcc_fit_ext(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                         in.pod_count.data(), uc.data(), um.data(), ext.R(), ext.alloc_x.data(),
+                         ext.used_x.data(), each.data(), n, 1, &specs[0].cpu, &specs[0].mem,
+                         x0.data(), qs.data(), es.data());
+    } else {
+      rc = kcc_fit_rows(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                        in.pod_count.data(), uc.data(), um.data(), specs[0].cpu, specs[0].mem,
+                        qs.data(), es.data());
+    }
     if (rc) return fail(ctx, rc);
     for (int64_t i = 0; i < n; ++i) {
       const int64_t q = qs[i];
@@ -259,7 +469,12 @@ int main(int argc, char** argv) {
     sc[s] = specs[s].cpu;
     sm[s] = specs[s].mem;
   }
-  if (schedReq)
+  if (useExt)
+    rc = kcc_fit_ext(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                     in.pod_count.data(), euc.data(), eum.data(), ext.R(), ext.alloc_x.data(),
+                     ext.used_x.data(), nullptr, 1, S, sc.data(), sm.data(), ext.spec_x.data(),
+                     totals.data(), serr.data());
+  else if (schedReq)
     rc = kcc_fit(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
                  in.pod_count.data(), suc.data(), sum_.data(), (int64_t)specs.size(), sc.data(),
                  sm.data(), totals.data(), serr.data());
@@ -299,10 +514,16 @@ int main(int argc, char** argv) {
     }
     ptot.resize(pools.size() * specs.size());
     perr.resize(pools.size() * specs.size());
-    rc = kcc_fit_grouped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
-                         in.pod_count.data(), uc.data(), um.data(), group.data(),
-                         (int64_t)pools.size(), (int64_t)specs.size(), sc.data(), sm.data(),
-                         ptot.data(), perr.data());
+    if (useExt)
+      rc = kcc_fit_ext(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                       in.pod_count.data(), uc.data(), um.data(), ext.R(), ext.alloc_x.data(),
+                       ext.used_x.data(), group.data(), (int64_t)pools.size(), S, sc.data(),
+                       sm.data(), ext.spec_x.data(), ptot.data(), perr.data());
+    else
+      rc = kcc_fit_grouped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                           in.pod_count.data(), uc.data(), um.data(), group.data(),
+                           (int64_t)pools.size(), (int64_t)specs.size(), sc.data(), sm.data(),
+                           ptot.data(), perr.data());
     if (rc) return fail(ctx, rc);
   }
   auto printPools = [&](size_t s) {

@@ -123,6 +123,17 @@ bool loadCluster(const std::string& path, Cluster& out, std::string& err) {
     } else if (kind == "pool") {
       if (out.nodes.empty()) return bad("pool before any node");
       if (!(is >> out.nodes.back().pool)) return bad("pool <name>");
+    } else if (kind == "resource") {
+      if (out.nodes.empty()) return bad("resource before any node");
+      std::string name, amount;
+      if (!(is >> name >> amount)) return bad("resource <name> <allocatable>");
+      out.nodes.back().resources.emplace_back(name, amount);
+    } else if (kind == "request") {
+      if (out.pods.empty() || out.pods.back().containers.empty())
+        return bad("request before any container");
+      std::string name, amount;
+      if (!(is >> name >> amount)) return bad("request <name> <amount>");
+      out.pods.back().containers.back().requests.emplace_back(name, amount);
     } else if (kind == "pod") {
       Pod p;
       if (!(is >> p.nodeName >> p.ns >> p.name >> p.phase)) return bad("pod <node|-> <ns> <name> <phase>");
@@ -274,6 +285,7 @@ int buildInputs(kcc_ctx* ctx, const Cluster& c, const std::vector<node>& rows, E
         off.push_back((int64_t)chars.size());
         in.mem_req.push_back(ct.memRequest);
         in.mem_lim.push_back(ct.memLimit);
+        in.app.push_back(&ct);
       }
       for (const Container& ct : p.containers) {  // opt-in model: init containers
         if (!ct.init) continue;

@@ -41,6 +41,8 @@ struct Container {
   std::string cpuRequest = "0", cpuLimit = "0";  // Quantity.String() (canonical)
   int64_t memRequest = 0, memLimit = 0;          // Quantity.Value()
   bool init = false, restartable = false;        // an init container (restartPolicy Always)
+  // Resources.Requests[name] of extended resources, Quantity.String() (`request` lines)
+  std::vector<std::pair<std::string, std::string>> requests;
 };
 
 struct Pod {
@@ -56,6 +58,8 @@ struct NodeObj {
   int64_t pods = 0;               // Status.Allocatable.Pods().Value()
   std::vector<std::string> conditions;  // Status.Conditions[j].Status
   std::string pool = "-";               // opaque node-pool name (`pool` line; "-": none given)
+  // Status.Allocatable[name] of extended resources, Quantity.String() (`resource` lines)
+  std::vector<std::pair<std::string, std::string>> resources;
 };
 
 struct Cluster {
@@ -66,12 +70,16 @@ struct Cluster {
 // Cluster description file (one object per line, '#' comments):
 //   node <name> <cpu> <memory> <pods> <cond0> <cond1> <cond2> <cond3>
 //   pool <name>                       (of the last node; a node without one is in pool "-")
+//   resource <name> <allocatable>     (of the last node: an extended resource, e.g. amd.com/gpu 8)
 //   pod <nodeName|-> <namespace> <name> <phase> [missing]
 //   container <cpuRequest> <cpuLimit> <memRequestBytes> <memLimitBytes>   (of the last pod)
 //   initcontainer <cpuRequest> <cpuLimit> <memRequestBytes> <memLimitBytes> [always]
 //   overhead <cpuMillis> <memBytes>                                         (of the last pod)
+//   request <name> <amount>           (of the last container: its request of an extended resource)
 // (init containers and overhead are read only by -schedulerRequests; the
-// reference's sums ignore them, CC:277; the pool name is read only by -byPool.)
+// reference's sums ignore them, CC:277; the pool name is read only by -byPool; `resource` and
+// `request` amounts are Quantity strings read only when a spec requests an extended resource,
+// and a `request` on an init container is never read.)
 // "-" as nodeName means "" (an unscheduled pod).  Returns false with a message on error.
 bool loadCluster(const std::string& path, Cluster& out, std::string& err);
 
@@ -102,6 +110,9 @@ struct EngineInputs {
   std::vector<uint64_t> init_cpu, ovh_cpu;
   std::vector<int64_t> init_mem, ovh_mem;
   std::vector<uint8_t> init_rst;
+  // the app container behind each CSR entry (cpu_req[k], mem_req[k]): the CLI builds the
+  // per-container columns of the extended resources from its `request` lines
+  std::vector<const Container*> app;
 };
 // The container cpu strings (limits and requests, CC:279-283) are converted on the device
 // in one kcc_parse_cpu_millis batch on `ctx`; each failed string prints

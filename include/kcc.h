@@ -462,6 +462,54 @@ int kcc_fit_grouped_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc
                           int64_t* d_totals, int32_t* d_spec_err, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Fit with extended resources.  The reference counts CPU and memory only (CC:119-133); a
+ * pod also requests ephemeral-storage, hugepages-* and device-plugin resources
+ * (amd.com/gpu, nvidia.com/gpu), and min(freeCPU / c, freeMem / m, freeGPU / g, ...) per
+ * node is not a sum of anything the other entry points return.  OPT-IN: with n_ext == 0
+ * this is kcc_fit (group == NULL) or kcc_fit_grouped, bit for bit.
+ *   n_ext = R extra resources, 0 <= R <= KCC_EXT_MAX, all int64 (Quantity.Value()):
+ *     alloc_x[r * n_nodes + i], used_x[r * n_nodes + i]  node row i, resource r
+ *     spec_x[r * n_specs + s]                             spec s, resource r
+ *   An extra resource behaves as the memory column (CC:125-130) except that a zero request
+ *   means "not requested": no constraint and no panic.  For row i and spec s:
+ *     qc, qm and the divide-by-zero rule exactly as kcc_fit;  q = findMin(qc, qm)  (CC:133)
+ *     for each r with x = spec_x[r][s] != 0:
+ *       fx = alloc_x <= used_x ? 0 : alloc_x - used_x         (int64, the difference wraps)
+ *       qx = fx == 0 ? 0 : fx / x   (Go int64 '/': truncating, MinInt64 / -1 == MinInt64)
+ *       q  = findMin(q, qx)                                                       (signed)
+ *     if q >= alloc_pods[i]: q = alloc_pods[i] - pod_count[i]     (CC:134-136, after the mins)
+ *     totals[s] += q                                                               (wraps)
+ *   A negative x takes the arithmetic of a negative memory request.  spec_err is
+ *   KCC_SPEC_DIVZERO under kcc_fit's rule only; an extra resource never raises it.
+ *   group / n_groups as in kcc_fit_grouped (cells [g * S + s], ids outside [0, G) skipped,
+ *   a per-cell flag, an empty group 0 / 0); group == NULL requires n_groups == 1 and puts
+ *   every row in group 0 (no sort is run).
+ * n_groups * n_specs <= 2^28, n_nodes <= 2^31 - 4096; n_ext outside [0, KCC_EXT_MAX], a NULL
+ * extra array with n_ext > 0, group == NULL with n_groups != 1: KCC_EINVAL.  n_nodes == 0 or
+ * n_specs == 0: KCC_OK, every output 0.  Host and async forms as kcc_fit_grouped's: the
+ * host form runs on the context's device 0 and retains no caller pointer; the async form
+ * only enqueues, allocates only when a size exceeds every earlier call's, never
+ * synchronises.  No kernel of it waits on another workgroup: it neither sets nor reads the
+ * fault words.
+ * ------------------------------------------------------------------------- */
+#define KCC_EXT_MAX 4
+int kcc_fit_ext(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+                const int64_t* alloc_pods, const int64_t* pod_count, const uint64_t* used_cpu,
+                const int64_t* used_mem, int64_t n_ext, const int64_t* alloc_x /* [R * N] */,
+                const int64_t* used_x /* [R * N] */, const int32_t* group /* nullable */,
+                int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
+                const int64_t* spec_mem, const int64_t* spec_x /* [R * S] */,
+                int64_t* totals /* [G * S] */, int32_t* spec_err /* [G * S] */);
+int kcc_fit_ext_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                      const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
+                      const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                      const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                      const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                      int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                      const int64_t* d_spec_x, int64_t* d_totals, int32_t* d_spec_err,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------
  * OPT-IN scheduler request model — explicitly NOT the
  * reference's semantics: the reference sums only the app containers of a node's pods
  * (CC:276-294, kcc_reduce_requests above; that stays the default).  This gives the

@@ -5,9 +5,10 @@ The compute lives in libkcc.so (hand-written gfx950 HIP kernels behind the C-ABI
 include/kcc.h).  Importing this package does not touch the GPU; constructing a
 CapacityEngine loads libkcc.so and fails loudly if it is missing.
 """
+from ._lib import KCC_EXT_MAX  # noqa: F401  (extra resources of CapacityEngine.fit_ext)
 from .engine import CapacityEngine, KccError, RequestSums, select_groups, verdict  # noqa: F401
 from .shard import node_range, shard_bounds  # noqa: F401
 
 __all__ = ["CapacityEngine", "KccError", "RequestSums", "verdict", "select_groups",
            "node_range",
-           "shard_bounds"]
+           "shard_bounds", "KCC_EXT_MAX"]

@@ -28,6 +28,7 @@ ERROR_NAMES = {
 KCC_SPEC_OK = 0
 KCC_SPEC_DIVZERO = 1
 KCC_SPEC_FAULT = 2
+KCC_EXT_MAX = 4  # include/kcc.h: extra resources of kcc_fit_ext
 
 _i64, _i32, _int, _vp, _dbl = C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_double
 
@@ -84,6 +85,9 @@ SIGNATURES = {
     "kcc_fit_rows": (_int, [_vp, _i64] + [_vp] * 6 + [C.c_uint64, _i64, _vp, _vp]),
     "kcc_fit_grouped": (_int, [_vp, _i64] + [_vp] * 7 + [_i64, _i64] + [_vp] * 4),
     "kcc_fit_grouped_async": (_int, [_vp, _i64] + [_vp] * 7 + [_i64, _i64] + [_vp] * 5),
+    "kcc_fit_ext": (_int, [_vp, _i64] + [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64, _i64] + [_vp] * 5),
+    "kcc_fit_ext_async": (_int, [_vp, _i64] + [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64, _i64]
+                          + [_vp] * 6),
     "kcc_pod_requests": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 11),
     "kcc_pod_requests_async": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 12),
     "kcc_reduce_requests_pods": (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 12),

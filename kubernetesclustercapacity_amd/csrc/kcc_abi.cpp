@@ -107,6 +107,8 @@ struct Dev {
   DevBuf k_key;                        // kcc_*_keyed staging
   DevBuf g_group;                                       // kcc_fit_grouped staging (group ids)
   DevBuf g_count, g_cursor, g_total, g_rec, g_rg, g_acc;  // kcc::GrpWork (grouped fit)
+  DevBuf x_alloc, x_used, x_spec;  // kcc_fit_ext staging (the extra columns)
+  DevBuf x_rec;                    // kcc::ExtWork::xrec (the other buffers are GrpWork's)
   DevBuf kb_counts, kb_tot, kb_sr, kb_sv;  // kcc::KeyedWork (bucketed keyed reduce)
   DevBuf kb_part, kb_arrive;               // one-sweep gather: part rows, arrivals (zeroed)
   DevBuf kb_esc_n, kb_esc_row, kb_esc_cpu, kb_esc_mem;
@@ -1022,7 +1024,8 @@ void kcc_destroy(kcc_ctx* ctx) {
                       &dv.q_iptr,    &dv.q_icpu,    &dv.q_imem,    &dv.q_rst,     &dv.q_ocpu,
                       &dv.q_omem,    &dv.q_pcpu,    &dv.q_pmem,
                       &dv.g_group,   &dv.g_count,   &dv.g_cursor,  &dv.g_total,   &dv.g_rec,
-                      &dv.g_rg,      &dv.g_acc};
+                      &dv.g_rg,      &dv.g_acc,     &dv.x_alloc,   &dv.x_used,    &dv.x_spec,
+                      &dv.x_rec};
     for (DevBuf* b : bufs)
       if (b->p) (void)hipFree(b->p);
     if (dv.stream) (void)hipStreamDestroy(dv.stream);
@@ -1936,6 +1939,144 @@ int kcc_fit_grouped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
                        as<uint64_t>(dv.used_cpu), as<int64_t>(dv.used_mem), as<int32_t>(dv.g_group),
                        n_groups, n_specs, as<uint64_t>(dv.spec_cpu), as<int64_t>(dv.spec_mem),
                        as<int64_t>(dv.totals), as<int32_t>(dv.err), dv.stream);
+  if (rc) return rc;
+  KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
+  KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
+  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
+  return KCC_OK;
+}
+
+}  // extern "C"
+
+
+// ---- fit with extended resources (kcc_ext.hip) ----------------------------------------
+
+namespace {
+
+// Argument checks of both ext entry points (host or device pointers alike).
+int check_ext(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+              const int64_t* alloc_pods, const int64_t* pod_count, const uint64_t* used_cpu,
+              const int64_t* used_mem, int64_t n_ext, const int64_t* alloc_x,
+              const int64_t* used_x, const int32_t* group, int64_t n_groups, int64_t n_specs,
+              const uint64_t* spec_cpu, const int64_t* spec_mem, const int64_t* spec_x,
+              const int64_t* totals, const int32_t* spec_err) {
+  if (n_nodes < 0 || n_specs < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (n_ext < 0 || n_ext > KCC_EXT_MAX) return fail(ctx, KCC_EINVAL, "n_ext must be in [0, KCC_EXT_MAX]");
+  if (n_groups < 1) return fail(ctx, KCC_EINVAL, "n_groups must be at least 1");
+  if (!group && n_groups != 1) return fail(ctx, KCC_EINVAL, "group is NULL: n_groups must be 1");
+  if (n_nodes > kcc::GRP_MAX_NODES) return fail(ctx, KCC_EINVAL, "too many nodes (max 2^31 - 4096)");
+  if (n_specs > kcc::GRP_MAX_CELLS || n_groups > kcc::GRP_MAX_CELLS ||
+      n_groups * n_specs > kcc::GRP_MAX_CELLS)
+    return fail(ctx, KCC_EINVAL, "too many cells: n_groups x n_specs must not exceed 2^28");
+  if (n_specs > 0 && (!spec_cpu || !spec_mem || !totals || !spec_err))
+    return fail(ctx, KCC_EINVAL, "NULL spec array / output");
+  if (n_nodes > 0 && (!alloc_cpu || !alloc_mem || !alloc_pods || !pod_count || !used_cpu || !used_mem))
+    return fail(ctx, KCC_EINVAL, "NULL node array");
+  if (n_ext > 0 && ((n_nodes > 0 && (!alloc_x || !used_x)) || (n_specs > 0 && !spec_x)))
+    return fail(ctx, KCC_EINVAL, "NULL extra-resource array with n_ext > 0");
+  return KCC_OK;
+}
+
+int fit_ext_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, const uint64_t* alloc_cpu,
+                const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
+                const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
+                const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
+                const int64_t* spec_mem, const int64_t* spec_x, int64_t* totals,
+                int32_t* spec_err, hipStream_t s) {
+  int rc = check_ext(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                     n_ext, alloc_x, used_x, group, n_groups, n_specs, spec_cpu, spec_mem, spec_x,
+                     totals, spec_err);
+  if (rc) return rc;
+  if (n_specs == 0) return KCC_OK;
+  const size_t cells = (size_t)(n_groups * n_specs);
+  if (n_nodes == 0) {
+    KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * cells, s));
+    KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * cells, s));
+    return KCC_OK;
+  }
+  if (kcc::grp_runs(n_nodes) * ((n_specs + kcc::GRP_PAIR_THREADS - 1) / kcc::GRP_PAIR_THREADS) >
+      0x7fffffff)
+    return fail(ctx, KCC_EINVAL, "n_nodes x n_specs beyond one launch (2^31 - 1 workgroups of 256 x 256 pairs)");
+  if (group) {
+    KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)n_groups));
+    KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)n_groups));
+    KCC_HIP(ctx, ensure(dv.g_total, 16));
+  }
+  KCC_HIP(ctx, ensure(dv.g_rec, sizeof(kcc::GrpRow) * (size_t)n_nodes));
+  KCC_HIP(ctx, ensure(dv.g_rg, 4 * (size_t)n_nodes));
+  KCC_HIP(ctx, ensure(dv.g_acc, 16 * cells));
+  KCC_HIP(ctx, ensure(dv.x_rec, sizeof(kcc::ExtCol) * (size_t)n_nodes * (size_t)n_ext));
+  const kcc::ExtWork w{{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor), as<uint32_t>(dv.g_total),
+                        as<kcc::GrpRow>(dv.g_rec), as<int32_t>(dv.g_rg), as<int64_t>(dv.g_acc)},
+                       as<kcc::ExtCol>(dv.x_rec)};
+  KCC_HIP(ctx, kcc::launch_fit_ext(n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
+                                   used_mem, (int)n_ext, alloc_x, used_x, group, n_groups, n_specs,
+                                   spec_cpu, spec_mem, spec_x, w, totals, spec_err, s));
+  return KCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kcc_fit_ext_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                      const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
+                      const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                      const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                      const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                      int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                      const int64_t* d_spec_x, int64_t* d_totals, int32_t* d_spec_err,
+                      void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  return fit_ext_dev(ctx, dv, n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count,
+                     d_used_cpu, d_used_mem, n_ext, d_alloc_x, d_used_x, d_group, n_groups, n_specs,
+                     d_spec_cpu, d_spec_mem, d_spec_x, d_totals, d_spec_err,
+                     static_cast<hipStream_t>(stream));
+}
+
+int kcc_fit_ext(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+                const int64_t* alloc_pods, const int64_t* pod_count, const uint64_t* used_cpu,
+                const int64_t* used_mem, int64_t n_ext, const int64_t* alloc_x,
+                const int64_t* used_x, const int32_t* group, int64_t n_groups, int64_t n_specs,
+                const uint64_t* spec_cpu, const int64_t* spec_mem, const int64_t* spec_x,
+                int64_t* totals, int32_t* spec_err) {
+  if (!ctx) return KCC_EINVAL;
+  int rc = check_ext(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                     n_ext, alloc_x, used_x, group, n_groups, n_specs, spec_cpu, spec_mem, spec_x,
+                     totals, spec_err);
+  if (rc) return rc;
+  if (n_specs == 0) return KCC_OK;
+  const size_t cells = (size_t)(n_groups * n_specs);
+  if (n_nodes == 0) {
+    memset(totals, 0, 8 * cells);
+    memset(spec_err, 0, 4 * cells);
+    return KCC_OK;
+  }
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  if ((rc = h2d(ctx, dv, dv.alloc_cpu, alloc_cpu, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.alloc_mem, alloc_mem, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.alloc_pods, alloc_pods, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.pod_count, pod_count, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.used_cpu, used_cpu, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.used_mem, used_mem, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.x_alloc, alloc_x, n_ext * n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.x_used, used_x, n_ext * n_nodes))) return rc;
+  if (group && (rc = h2d(ctx, dv, dv.g_group, group, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.spec_cpu, spec_cpu, n_specs))) return rc;
+  if ((rc = h2d(ctx, dv, dv.spec_mem, spec_mem, n_specs))) return rc;
+  if ((rc = h2d(ctx, dv, dv.x_spec, spec_x, n_ext * n_specs))) return rc;
+  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
+  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
+  rc = fit_ext_dev(ctx, dv, n_nodes, as<uint64_t>(dv.alloc_cpu), as<int64_t>(dv.alloc_mem),
+                   as<int64_t>(dv.alloc_pods), as<int64_t>(dv.pod_count), as<uint64_t>(dv.used_cpu),
+                   as<int64_t>(dv.used_mem), n_ext, as<int64_t>(dv.x_alloc), as<int64_t>(dv.x_used),
+                   group ? as<int32_t>(dv.g_group) : nullptr, n_groups, n_specs,
+                   as<uint64_t>(dv.spec_cpu), as<int64_t>(dv.spec_mem), as<int64_t>(dv.x_spec),
+                   as<int64_t>(dv.totals), as<int32_t>(dv.err), dv.stream);
   if (rc) return rc;
   KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
   KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));

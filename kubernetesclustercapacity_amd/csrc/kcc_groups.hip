@@ -29,14 +29,6 @@
 namespace kcc {
 namespace {
 
-constexpr int GRP_SORT_THREADS = 1024;  // rows per workgroup of grp_hist / grp_scatter
-constexpr int GRP_ROW_FAST = 1 << 30;   // rg[]: the row's group, and this bit for a fast row
-constexpr uint64_t GRP_FC_MAX = 1ull << 31;  // fast rows: free CPU below this
-constexpr uint64_t GRP_FM_MAX = 1ull << 50;  // fast rows: free memory below this (and >= 0)
-constexpr uint64_t GRP_SPEC_MAX = 1ull << 52;  // fast specs: 1 <= c, m <= this
-
-__device__ inline bool grp_valid(int32_t g, int64_t G) { return g >= 0 && (int64_t)g < G; }
-
 // count[g] += rows of group g.  lds != 0 (G <= GRP_LDS_GROUPS): summed in LDS first.
 __global__ __launch_bounds__(GRP_SORT_THREADS) void grp_hist_kernel(
     int64_t n, int64_t G, const int32_t* __restrict__ group, uint32_t* __restrict__ count,
@@ -131,21 +123,6 @@ __global__ __launch_bounds__(GRP_SORT_THREADS) void grp_scatter_kernel(
   rg[pos] = g | (fast ? GRP_ROW_FAST : 0);
 }
 
-// floor(f / d) for integers 0 <= f < 2^50, 1 <= d <= 2^52 held exactly in f64; rd = 1.0 / d.
-__device__ inline double grp_div(double f, double d, double rd) {
-  double t = __builtin_trunc(f * rd);
-  const double r = __builtin_fma(-t, d, f);  // exact: an integer of magnitude < 2 d
-  t = r < 0.0 ? t - 1.0 : t;
-  t = r >= d ? t + 1.0 : t;
-  return t;
-}
-
-__device__ inline void grp_flush(int64_t* __restrict__ acc, unsigned long long* __restrict__ cnt,
-                                 int64_t cell, bool live, int64_t sum, unsigned long long z) {
-  if (live) atomicAdd(reinterpret_cast<unsigned long long*>(acc) + cell, (unsigned long long)sum);
-  if (__any(z != 0) && live) atomicAdd(cnt + cell, z);
-}
-
 __global__ __launch_bounds__(GRP_PAIR_THREADS) void grp_pairs_kernel(
     const uint32_t* __restrict__ total, int64_t S, int64_t sblocks,
     const uint64_t* __restrict__ spec_cpu, const int64_t* __restrict__ spec_mem,
@@ -226,6 +203,26 @@ __global__ __launch_bounds__(256) void grp_finalize_kernel(int64_t cells, const 
 
 }  // namespace
 
+hipError_t launch_grp_count_scan(int64_t n, int64_t G, const int32_t* group, const GrpWork& w,
+                                 hipStream_t s) {
+  const int64_t sort_grid = (n + GRP_SORT_THREADS - 1) / GRP_SORT_THREADS;
+  const int lds = G <= GRP_LDS_GROUPS ? 1 : 0;
+  hipError_t e;
+  if ((e = hipMemsetAsync(w.count, 0, 4 * (size_t)G, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(grp_hist_kernel, dim3((unsigned)sort_grid), dim3(GRP_SORT_THREADS), 0, s, n, G,
+                     group, w.count, lds);
+  hipLaunchKernelGGL(grp_scan_kernel, dim3(1), dim3(1024), 0, s, G, w.count, w.cursor, w.total);
+  return hipGetLastError();
+}
+
+hipError_t launch_grp_finalize(int64_t cells, const int64_t* acc, const unsigned long long* cnt,
+                               int64_t* totals, int32_t* spec_err, hipStream_t s) {
+  const int64_t fin_grid = (cells + 255) / 256;
+  hipLaunchKernelGGL(grp_finalize_kernel, dim3((unsigned)fin_grid), dim3(256), 0, s, cells, acc,
+                     cnt, totals, spec_err);
+  return hipGetLastError();
+}
+
 hipError_t launch_fit_grouped(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
                               const int64_t* alloc_pods, const int64_t* pod_count,
                               const uint64_t* used_cpu, const int64_t* used_mem,
@@ -237,24 +234,19 @@ hipError_t launch_fit_grouped(int64_t n, const uint64_t* alloc_cpu, const int64_
   const int64_t sort_grid = (n + GRP_SORT_THREADS - 1) / GRP_SORT_THREADS;
   const int64_t sblocks = (S + GRP_PAIR_THREADS - 1) / GRP_PAIR_THREADS;
   const int64_t pair_grid = grp_runs(n) * sblocks;
-  const int64_t fin_grid = (cells + 255) / 256;
   if (cells > GRP_MAX_CELLS || n > GRP_MAX_NODES || pair_grid > 0x7fffffff) return hipErrorInvalidValue;
   const int lds = G <= GRP_LDS_GROUPS ? 1 : 0;
   hipError_t e;
-  if ((e = hipMemsetAsync(w.count, 0, 4 * (size_t)G, s)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(w.acc, 0, 16 * (size_t)cells, s)) != hipSuccess) return e;
   int64_t* acc = w.acc;
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(w.acc + cells);
-  hipLaunchKernelGGL(grp_hist_kernel, dim3((unsigned)sort_grid), dim3(GRP_SORT_THREADS), 0, s, n, G,
-                     group, w.count, lds);
-  hipLaunchKernelGGL(grp_scan_kernel, dim3(1), dim3(1024), 0, s, G, w.count, w.cursor, w.total);
+  if ((e = launch_grp_count_scan(n, G, group, w, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(grp_scatter_kernel, dim3((unsigned)sort_grid), dim3(GRP_SORT_THREADS), 0, s, n,
                      G, group, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
                      w.cursor, w.rec, w.rg, lds);
   hipLaunchKernelGGL(grp_pairs_kernel, dim3((unsigned)pair_grid), dim3(GRP_PAIR_THREADS), 0, s,
                      w.total, S, sblocks, spec_cpu, spec_mem, w.rec, w.rg, acc, cnt);
-  hipLaunchKernelGGL(grp_finalize_kernel, dim3((unsigned)fin_grid), dim3(256), 0, s, cells, acc,
-                     cnt, totals, spec_err);
+  if ((e = launch_grp_finalize(cells, acc, cnt, totals, spec_err, s)) != hipSuccess) return e;
   return hipGetLastError();
 }
 

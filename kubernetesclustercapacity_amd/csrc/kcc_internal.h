@@ -607,6 +607,64 @@ hipError_t launch_fit_grouped(int64_t n, const uint64_t* alloc_cpu, const int64_
                               const int64_t* spec_mem, const GrpWork& w, int64_t* totals,
                               int32_t* spec_err, hipStream_t s);
 
+// What kcc_groups.hip and kcc_ext.hip share: the sort's constants, the launches of the
+// kernels both use (they stay in kcc_groups.hip) and the pair loop's device helpers.
+constexpr int GRP_SORT_THREADS = 1024;  // rows per workgroup of the hist / scatter kernels
+constexpr int GRP_ROW_FAST = 1 << 30;   // rg[]: the row's group, and this bit for a fast row
+constexpr uint64_t GRP_FC_MAX = 1ull << 31;  // fast rows: free CPU below this
+constexpr uint64_t GRP_FM_MAX = 1ull << 50;  // fast rows: free memory below this (and >= 0)
+constexpr uint64_t GRP_SPEC_MAX = 1ull << 52;  // fast specs: 1 <= c, m <= this
+// grp_hist + grp_scan: w.count zeroed, then count / cursor / total filled from group[0..n).
+hipError_t launch_grp_count_scan(int64_t n, int64_t G, const int32_t* group, const GrpWork& w,
+                                 hipStream_t s);
+// grp_finalize over acc / cnt [cells].
+hipError_t launch_grp_finalize(int64_t cells, const int64_t* acc, const unsigned long long* cnt,
+                               int64_t* totals, int32_t* spec_err, hipStream_t s);
+
+#if defined(__HIPCC__)
+__device__ inline bool grp_valid(int32_t g, int64_t G) { return g >= 0 && (int64_t)g < G; }
+
+// floor(f / d) for integers 0 <= f < 2^50, 1 <= d <= 2^52 held exactly in f64; rd = 1.0 / d.
+__device__ inline double grp_div(double f, double d, double rd) {
+  double t = __builtin_trunc(f * rd);
+  const double r = __builtin_fma(-t, d, f);  // exact: an integer of magnitude < 2 d
+  t = r < 0.0 ? t - 1.0 : t;
+  t = r >= d ? t + 1.0 : t;
+  return t;
+}
+
+__device__ inline void grp_flush(int64_t* __restrict__ acc, unsigned long long* __restrict__ cnt,
+                                 int64_t cell, bool live, int64_t sum, unsigned long long z) {
+  if (live) atomicAdd(reinterpret_cast<unsigned long long*>(acc) + cell, (unsigned long long)sum);
+  if (__any(z != 0) && live) atomicAdd(cnt + cell, z);
+}
+#endif
+
+// ---- extended-resource fit (kcc_ext.hip) ---------------------------
+// Up to EXT_MAX extra int64 resources per row (resource-major columns) join findMin; a
+// zero request leaves its resource out.  The row record is GrpRow plus, per resource, one
+// ExtCol: the free amount (0 where alloc <= used) and, for a fast row (GrpRow's bounds and
+// 0 <= fx < 2^50 for every resource), the same value as f64.
+constexpr int EXT_MAX = 4;
+struct __attribute__((aligned(16))) ExtCol {
+  int64_t fx;
+  double fxd;
+};
+static_assert(sizeof(ExtCol) == 16, "ExtCol must be 16 B");
+struct ExtWork {
+  GrpWork g;    // count / cursor / total are used only with group ids
+  ExtCol* xrec;  // [n * R] record-major: the R columns of record p at xrec[p * R ...]
+};
+// group == nullptr: every row in group 0 (G must be 1), records in row order, no sort.
+// Every cell of totals / spec_err [G * S] is written.  n, G, S >= 1, 0 <= R <= EXT_MAX.
+hipError_t launch_fit_ext(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+                          const int64_t* alloc_pods, const int64_t* pod_count,
+                          const uint64_t* used_cpu, const int64_t* used_mem, int R,
+                          const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                          int64_t G, int64_t S, const uint64_t* spec_cpu, const int64_t* spec_mem,
+                          const int64_t* spec_x, const ExtWork& w, int64_t* totals,
+                          int32_t* spec_err, hipStream_t s);
+
 // ---- opt-in scheduler request model (kcc_pods.hip) ---------------
 hipError_t launch_pod_requests(int64_t n_pods, int64_t n_cont, int64_t n_init,
                                const int64_t* pod_ptr, const uint64_t* cpu_req,

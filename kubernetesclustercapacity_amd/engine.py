@@ -174,6 +174,58 @@ class CapacityEngine:
             _dp(used_cpu), _dp(used_mem), _dp(group), int(n_groups), s, _dp(spec_cpu),
             _dp(spec_mem), _dp(totals), _dp(spec_err), _stream(stream)))
 
+    def fit_ext(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                alloc_x, used_x, spec_cpu, spec_mem, spec_x, group=None, n_groups=1):
+        """The fit with R extra resources (GPUs, ephemeral storage, hugepages; opt-in, not
+        the reference's two-resource arithmetic): alloc_x / used_x int64 [R, N], spec_x
+        int64 [R, S].  An extra resource joins findMin as a second memory column, except
+        that a zero request leaves it out (no constraint, no panic); the pod-slot clamp
+        follows all the mins.  R = 0 is total_possible_max_replicas (group None) or
+        fit_grouped.  Returns (totals int64, err int32) of shape [S] without group ids and
+        [n_groups, S] with them."""
+        a = [_arr(alloc_cpu, np.uint64), _arr(alloc_mem, np.int64), _arr(alloc_pods, np.int64),
+             _arr(pod_count, np.int64), _arr(used_cpu, np.uint64), _arr(used_mem, np.int64)]
+        n = a[0].size
+        if any(x.size != n for x in a):
+            raise ValueError("node arrays differ in length")
+        sc, sm = _arr(spec_cpu, np.uint64), _arr(spec_mem, np.int64)
+        if sc.size != sm.size:
+            raise ValueError("spec arrays differ in length")
+        ax, ux, sx = _arr(alloc_x, np.int64), _arr(used_x, np.int64), _arr(spec_x, np.int64)
+        if ax.ndim != 2 or ux.shape != ax.shape or ax.shape[1] != n:
+            raise ValueError("alloc_x and used_x must both be [R, N]")
+        R = ax.shape[0]
+        if sx.shape != (R, sc.size):
+            raise ValueError("spec_x must be [R, S]")
+        G = int(n_groups)
+        if group is not None:
+            group = _key32(group)
+            if group.size != n:
+                raise ValueError("node arrays differ in length")
+        totals = np.zeros((max(G, 0), sc.size), np.int64)
+        err = np.zeros((max(G, 0), sc.size), np.int32)
+        self._check(self._lib.kcc_fit_ext(self._h, n, *[_p(x) for x in a], R, _p(ax), _p(ux),
+                                          _p(group), G, sc.size, _p(sc), _p(sm), _p(sx),
+                                          _p(totals), _p(err)))
+        if group is None:
+            return totals[0], err[0]
+        return totals, err
+
+    def fit_ext_async(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                      n_ext, alloc_x, used_x, group, n_groups, spec_cpu, spec_mem, spec_x,
+                      totals, spec_err, stream=None):
+        """Device form of fit_ext (torch tensors on the engine's device; alloc_x / used_x
+        int64 of n_ext * N elements, spec_x of n_ext * S, resource-major; group int32 or
+        None; totals int64 / spec_err int32 of n_groups * S elements).  The arguments go to
+        the C-ABI as they are (None: NULL), which validates them."""
+        n = 0 if alloc_cpu is None else alloc_cpu.numel()
+        s = 0 if spec_cpu is None else spec_cpu.numel()
+        self._check(self._lib.kcc_fit_ext_async(
+            self._h, n, _dp(alloc_cpu), _dp(alloc_mem), _dp(alloc_pods), _dp(pod_count),
+            _dp(used_cpu), _dp(used_mem), int(n_ext), _dp(alloc_x), _dp(used_x), _dp(group),
+            int(n_groups), s, _dp(spec_cpu), _dp(spec_mem), _dp(spec_x), _dp(totals),
+            _dp(spec_err), _stream(stream)))
+
     def capacity(self, node_ptr, cpu_req, mem_req, alloc_cpu, alloc_mem, alloc_pods, pod_count,
                  spec_cpu, spec_mem):
         """Fused (a)+(b) on host arrays.  Returns (totals, spec_err)."""
