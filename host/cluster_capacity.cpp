@@ -11,7 +11,13 @@
 // device-plugin GPUs, ephemeral-storage, hugepages — which the cluster file gives per node
 // as `resource` lines and per container as `request` lines; in a -specs file trailing
 // name=amount columns say the same per spec.  Totals, pools and -v's "Max replicas" then
-// come from kcc_fit_ext; the output format does not change).
+// come from kcc_fit_ext; the output format does not change), and the opt-in spread
+// constraints -maxPerNode k (at most k replicas on one node: required pod anti-affinity on the
+// hostname), -spreadBy zone with -maxSkew k (default 1; topologySpreadConstraints over the
+// cluster file's `zone` lines, DoNotSchedule).  They apply to every spec and compose with
+// -byPool (the pools' totals under the per-node cap) and -extRequests; the totals then come
+// from kcc_fit_capped and kcc_spread_fold, and with -spreadBy zone "Zone <name> : <used> of
+// <cap>" lines follow the total.  Without them the output is the reference's.
 #include <array>
 #include <cctype>
 #include <cerrno>
@@ -45,7 +51,8 @@ struct Flags {
       {"cpuLimits", "200m"},      {"memRequests", "100mb"}, {"memLimits", "200mb"},
       {"replicas", "1"},          {"specs", ""},            {"device", "0"},
       {"gpus", "1"},              {"v", "false"},           {"schedulerRequests", "false"},
-      {"byPool", "false"},        {"extRequests", ""}};
+      {"byPool", "false"},        {"extRequests", ""},      {"maxPerNode", "0"},
+      {"spreadBy", ""},           {"maxSkew", "1"}};
 };
 
 // Go flag package syntax: -name=value, -name value, --name=value; bool -v.
@@ -292,6 +299,26 @@ int main(int argc, char** argv) {
   // the totals per node pool (the cluster file's `pool` lines) after the reference's output
   const bool byPool = f.v["byPool"] == "true";
 
+  // opt-in spread constraints (NOT the reference's arithmetic)
+  int64_t maxPerNode = 0, maxSkew = 1;
+  if (!goAtoiStrict(f.v["maxPerNode"], maxPerNode) || maxPerNode < 0) {
+    std::fprintf(stderr, "invalid value \"%s\" for flag -maxPerNode: want a count (0: no cap)\n",
+                 f.v["maxPerNode"].c_str());
+    return 2;
+  }
+  if (!goAtoiStrict(f.v["maxSkew"], maxSkew) || maxSkew < 1) {
+    std::fprintf(stderr, "invalid value \"%s\" for flag -maxSkew: want a count of at least 1\n",
+                 f.v["maxSkew"].c_str());
+    return 2;
+  }
+  if (!f.v["spreadBy"].empty() && f.v["spreadBy"] != "zone") {
+    std::fprintf(stderr, "invalid value \"%s\" for flag -spreadBy: want zone\n",
+                 f.v["spreadBy"].c_str());
+    return 2;
+  }
+  const bool byZone = f.v["spreadBy"] == "zone";
+  const bool spread = byZone || maxPerNode > 0;
+
   Spec one{f.v["cpuRequests"], f.v["memRequests"], f.v["replicas"], 0, 0, 0, {}};
   if (!parseExtList(f.v["extRequests"], one.ext)) {
     std::fprintf(stderr, "invalid value \"%s\" for flag -extRequests: want name=amount[,name=amount...]\n",
@@ -485,6 +512,73 @@ int main(int argc, char** argv) {
                       totals.data(), serr.data());
   if (rc) return fail(ctx, rc);
 
+  // -maxPerNode / -spreadBy zone: the totals again under the spread constraints.  Row i is in
+  // the zone of node i (zones in first-appearance order; without -spreadBy one group);
+  // ztot / zerr [zone][spec] are the zones' capacities under the per-node cap.
+  std::vector<std::string> zones;
+  std::vector<int64_t> ztot, zrows;
+  std::vector<int32_t> zerr;
+  const std::vector<int64_t> caps(specs.size(), maxPerNode);
+  if (spread && n > 0) {
+    std::vector<int32_t> group;
+    if (byZone) {
+      std::map<std::string, int32_t> id;
+      group.resize((size_t)n);
+      for (int64_t i = 0; i < n; ++i) {
+        const std::string& name = cl.nodes[(size_t)i].zone;
+        auto it = id.find(name);
+        if (it == id.end()) {
+          it = id.emplace(name, (int32_t)zones.size()).first;
+          zones.push_back(name);
+        }
+        group[(size_t)i] = it->second;
+      }
+    }
+    const int64_t Z = byZone ? (int64_t)zones.size() : 1;
+    std::vector<uint64_t> uc(useExt ? euc : suc);
+    std::vector<int64_t> um(useExt ? eum : sum_);
+    if (!useExt && !schedReq) {  // the per-node request sums (CC:290-293)
+      uc.resize((size_t)n);
+      um.resize((size_t)n);
+      rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(),
+                               in.mem_req.data(), nullptr, nullptr, uc.data(), um.data(), nullptr,
+                               nullptr);
+      if (rc) return fail(ctx, rc);
+    }
+    ztot.resize((size_t)(Z * S));
+    zerr.resize((size_t)(Z * S));
+    zrows.resize((size_t)Z);
+    rc = kcc_fit_capped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                        in.pod_count.data(), uc.data(), um.data(), useExt ? ext.R() : 0,
+                        useExt ? ext.alloc_x.data() : nullptr, useExt ? ext.used_x.data() : nullptr,
+                        byZone ? group.data() : nullptr, Z, S, sc.data(), sm.data(),
+                        useExt ? ext.spec_x.data() : nullptr, ztot.data(), zerr.data(),
+                        caps.data(), nullptr, zrows.data());
+    if (rc) return fail(ctx, rc);
+    const std::vector<int64_t> skew(specs.size(), byZone ? maxSkew : 0);
+    rc = kcc_spread_fold(ctx, Z, S, ztot.data(), zerr.data(), zrows.data(), nullptr, Z, nullptr,
+                         skew.data(), totals.data(), serr.data());
+    if (rc) return fail(ctx, rc);
+  }
+  // "Zone <name> : <used> of <cap>": used = min(cap, the smallest zone's cap + maxSkew)
+  auto printZones = [&](size_t s) {
+    if (zones.empty()) return;
+    int64_t m = INT64_MAX;
+    for (size_t z = 0; z < zones.size(); ++z)
+      if (ztot[z * specs.size() + s] < m) m = ztot[z * specs.size() + s];
+    const int64_t lim = (m > 0 && maxSkew > INT64_MAX - m) ? INT64_MAX : m + maxSkew;
+    for (size_t z = 0; z < zones.size(); ++z) {
+      const int64_t cap = ztot[z * specs.size() + s];
+      if (zerr[z * specs.size() + s])
+        std::printf("Zone %s : panic: runtime error: integer divide by zero\n", zones[z].c_str());
+      else if (serr[s])
+        std::printf("Zone %s : - of %" PRId64 "\n", zones[z].c_str(), cap);
+      else
+        std::printf("Zone %s : %" PRId64 " of %" PRId64 "\n", zones[z].c_str(), cap <= lim ? cap : lim,
+                    cap);
+    }
+  };
+
   // -byPool: row i is in the pool of node i (an unhealthy node's zero row stays in its
   // node's pool); pools in first-appearance order; ptot / perr [pool][spec]
   std::vector<std::string> pools;
@@ -514,7 +608,15 @@ int main(int argc, char** argv) {
     }
     ptot.resize(pools.size() * specs.size());
     perr.resize(pools.size() * specs.size());
-    if (useExt)
+    if (maxPerNode > 0)  // the pools under the per-node cap
+      rc = kcc_fit_capped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                          in.pod_count.data(), uc.data(), um.data(), useExt ? ext.R() : 0,
+                          useExt ? ext.alloc_x.data() : nullptr,
+                          useExt ? ext.used_x.data() : nullptr, group.data(),
+                          (int64_t)pools.size(), S, sc.data(), sm.data(),
+                          useExt ? ext.spec_x.data() : nullptr, ptot.data(), perr.data(),
+                          caps.data(), nullptr, nullptr);
+    else if (useExt)
       rc = kcc_fit_ext(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
                        in.pod_count.data(), uc.data(), um.data(), ext.R(), ext.alloc_x.data(),
                        ext.used_x.data(), group.data(), (int64_t)pools.size(), S, sc.data(),
@@ -552,6 +654,7 @@ int main(int argc, char** argv) {
                   " replicas. Please try again by reducing the number of replicas or/and cpu/memory "
                   "resource requests. Exiting!!\n\n", specs[0].replicas);
     std::printf("%s\n", kRule);
+    printZones(0);
     printPools(0);
     return 0;
   }
@@ -563,6 +666,7 @@ int main(int argc, char** argv) {
     else
       std::printf("%s %s %s total=%" PRId64 " %s\n", specs[s].cpuStr.c_str(), specs[s].memStr.c_str(),
                   specs[s].repStr.c_str(), totals[s], totals[s] >= specs[s].replicas ? "yes" : "no");
+    printZones(s);  // (-spreadBy zone: this spec's zones under its line)
     printPools(s);  // (-byPool: this spec's pools under its line)
   }
   return 0;

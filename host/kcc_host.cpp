@@ -123,6 +123,9 @@ bool loadCluster(const std::string& path, Cluster& out, std::string& err) {
     } else if (kind == "pool") {
       if (out.nodes.empty()) return bad("pool before any node");
       if (!(is >> out.nodes.back().pool)) return bad("pool <name>");
+    } else if (kind == "zone") {
+      if (out.nodes.empty()) return bad("zone before any node");
+      if (!(is >> out.nodes.back().zone)) return bad("zone <name>");
     } else if (kind == "resource") {
       if (out.nodes.empty()) return bad("resource before any node");
       std::string name, amount;

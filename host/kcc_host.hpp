@@ -58,6 +58,7 @@ struct NodeObj {
   int64_t pods = 0;               // Status.Allocatable.Pods().Value()
   std::vector<std::string> conditions;  // Status.Conditions[j].Status
   std::string pool = "-";               // opaque node-pool name (`pool` line; "-": none given)
+  std::string zone = "-";               // topology zone (`zone` line; "-": none given)
   // Status.Allocatable[name] of extended resources, Quantity.String() (`resource` lines)
   std::vector<std::pair<std::string, std::string>> resources;
 };
@@ -70,6 +71,7 @@ struct Cluster {
 // Cluster description file (one object per line, '#' comments):
 //   node <name> <cpu> <memory> <pods> <cond0> <cond1> <cond2> <cond3>
 //   pool <name>                       (of the last node; a node without one is in pool "-")
+//   zone <name>                       (of the last node; a node without one is in zone "-")
 //   resource <name> <allocatable>     (of the last node: an extended resource, e.g. amd.com/gpu 8)
 //   pod <nodeName|-> <namespace> <name> <phase> [missing]
 //   container <cpuRequest> <cpuLimit> <memRequestBytes> <memLimitBytes>   (of the last pod)

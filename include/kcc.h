@@ -510,6 +510,91 @@ int kcc_fit_ext_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu
                       void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Spread constraints in the fit: a per-node cap and a maxSkew over topology domains.  A
+ * Deployment with required pod anti-affinity on the hostname ("at most k per node") or with
+ * topologySpreadConstraints (whenUnsatisfiable: DoNotSchedule) holds fewer replicas than the
+ * plain sum the other entry points report: three zones with room for 10, 4 and 7 and
+ * maxSkew 1 hold 5 + 4 + 5 = 14, not 21.  OPT-IN, not the reference's arithmetic: with
+ * node_cap, cell_min and group_rows all NULL, kcc_fit_capped is kcc_fit_ext bit for bit (it
+ * launches the same kernels).
+ *
+ * kcc_fit_capped: kcc_fit_ext's arguments in its order, then
+ *   node_cap[s]      (nullable) cap on one node's count for spec s; <= 0 or NULL: no cap
+ *   cell_min[g*S+s]  (nullable output) the minimum of q over the cell's rows, before the cap
+ *   group_rows[g]    (nullable output) rows with group id g; group == NULL: group_rows[0] =
+ *                    n_nodes
+ * For row i and spec s:
+ *     q as kcc_fit_ext up to and including the pod-slot clamp (CC:134-136, after all the mins)
+ *     qmin[cell] = signed min(qmin[cell], q)                            (before the cap)
+ *     if node_cap[s] > 0 and q > node_cap[s]: q = node_cap[s]    (signed, after the clamp)
+ *     totals[cell] += q                                                          (wraps)
+ *   The cap follows the clamp because the clamp's value allocatablePods - len(pods) is a
+ *   count of pods on that node too.  spec_err follows kcc_fit's rule unchanged; a flagged
+ *   cell has totals 0 and cell_min 0; a cell with no rows has totals 0, err 0 and cell_min
+ *   INT64_MAX (the identity of the min).  Argument errors and size limits are kcc_fit_ext's.
+ *   n_nodes == 0: totals / spec_err 0, cell_min INT64_MAX, group_rows 0.  n_specs == 0: no
+ *   cell is written; group_rows still is.
+ *
+ * kcc_spread_fold: the G x S cells (of kcc_fit_capped, kcc_fit_ext or kcc_fit_grouped) to
+ * one total per spec.  domain_of[g] (int32, nullable: group g is its own domain, and then
+ * n_domains must equal n_groups) maps groups to D topology domains, many to one, so that a
+ * selector and a spread combine: groups are (pool, zone) pairs, domains are zones, eligible
+ * picks the pools.  Per spec s:
+ *   group g is live iff group_rows[g] > 0 (NULL: every group), eligible[g*S+s] != 0 (uint8;
+ *     NULL: all) and domain_of[g] in [0, D) (other ids are skipped);
+ *   spec_err[s] = KCC_SPEC_DIVZERO and totals[s] = 0 iff a live group's cell is flagged;
+ *   cap_d = the wrapping sum of the live cells of domain d; d is present iff it has a live
+ *     group (an empty pool is not a domain; a pool whose nodes are all full is one, with
+ *     cap 0 — that is why spread constraints bite);
+ *   no present domain: totals[s] = 0;
+ *   max_skew[s] <= 0 (or max_skew NULL): totals[s] = the wrapping sum of the present cap_d
+ *     (the sum of the live cells: the selector's answer);
+ *   else m = signed min of cap_d over the present domains, lim = m + max_skew[s] saturating
+ *     at INT64_MAX, totals[s] = the wrapping sum over the present domains of
+ *     (cap_d <= lim ? cap_d : lim).
+ * n_groups * n_specs <= 2^28, 1 <= n_domains, n_domains * n_specs <= 2^28, domain_of == NULL
+ * with n_domains != n_groups, a negative size: KCC_EINVAL.  n_groups == 0 or n_specs == 0
+ * (checked before n_domains): KCC_OK, outputs 0.
+ *
+ * Host and async forms as kcc_fit_ext's: the host forms run on the context's device 0 and
+ * retain no caller pointer; the async forms take device pointers, only enqueue, allocate
+ * only when a size exceeds every earlier call's and never synchronise (no readback between
+ * the pair pass and the fold: both can be captured into one graph).  No kernel of either
+ * waits on another workgroup: they neither set nor read the fault words.
+ * ------------------------------------------------------------------------- */
+int kcc_fit_capped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                   const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
+                   const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
+                   const int64_t* alloc_x /* [R * N] */, const int64_t* used_x /* [R * N] */,
+                   const int32_t* group /* nullable */, int64_t n_groups, int64_t n_specs,
+                   const uint64_t* spec_cpu, const int64_t* spec_mem,
+                   const int64_t* spec_x /* [R * S] */, int64_t* totals /* [G * S] */,
+                   int32_t* spec_err /* [G * S] */, const int64_t* node_cap /* [S], nullable */,
+                   int64_t* cell_min /* [G * S], nullable */,
+                   int64_t* group_rows /* [G], nullable */);
+int kcc_fit_capped_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                         const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
+                         const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                         const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                         const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                         int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                         const int64_t* d_spec_x, int64_t* d_totals, int32_t* d_spec_err,
+                         const int64_t* d_node_cap, int64_t* d_cell_min, int64_t* d_group_rows,
+                         void* stream);
+int kcc_spread_fold(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs,
+                    const int64_t* cell_totals /* [G * S] */, const int32_t* cell_err /* [G * S] */,
+                    const int64_t* group_rows /* [G], nullable */,
+                    const int32_t* domain_of /* [G], nullable */, int64_t n_domains,
+                    const uint8_t* eligible /* [G * S], nullable */,
+                    const int64_t* max_skew /* [S], nullable */, int64_t* totals /* [S] */,
+                    int32_t* spec_err /* [S] */);
+int kcc_spread_fold_async(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs,
+                          const int64_t* d_cell_totals, const int32_t* d_cell_err,
+                          const int64_t* d_group_rows, const int32_t* d_domain_of,
+                          int64_t n_domains, const uint8_t* d_eligible, const int64_t* d_max_skew,
+                          int64_t* d_totals, int32_t* d_spec_err, void* stream);
+
+/* ---------------------------------------------------------------------------
  * OPT-IN scheduler request model — explicitly NOT the
  * reference's semantics: the reference sums only the app containers of a node's pods
  * (CC:276-294, kcc_reduce_requests above; that stays the default).  This gives the

@@ -88,6 +88,12 @@ SIGNATURES = {
     "kcc_fit_ext": (_int, [_vp, _i64] + [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64, _i64] + [_vp] * 5),
     "kcc_fit_ext_async": (_int, [_vp, _i64] + [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64, _i64]
                           + [_vp] * 6),
+    "kcc_fit_capped": (_int, [_vp, _i64] + [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64, _i64]
+                       + [_vp] * 8),
+    "kcc_fit_capped_async": (_int, [_vp, _i64] + [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64, _i64]
+                             + [_vp] * 9),
+    "kcc_spread_fold": (_int, [_vp, _i64, _i64] + [_vp] * 4 + [_i64] + [_vp] * 4),
+    "kcc_spread_fold_async": (_int, [_vp, _i64, _i64] + [_vp] * 4 + [_i64] + [_vp] * 5),
     "kcc_pod_requests": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 11),
     "kcc_pod_requests_async": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 12),
     "kcc_reduce_requests_pods": (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 12),

@@ -109,6 +109,10 @@ struct Dev {
   DevBuf g_count, g_cursor, g_total, g_rec, g_rg, g_acc;  // kcc::GrpWork (grouped fit)
   DevBuf x_alloc, x_used, x_spec;  // kcc_fit_ext staging (the extra columns)
   DevBuf x_rec;                    // kcc::ExtWork::xrec (the other buffers are GrpWork's)
+  DevBuf sp_qmin;                  // kcc_fit_capped: the pre-finalize minima [G S]
+  DevBuf sp_cap, sp_cmin, sp_grows;  // kcc_fit_capped staging (node_cap; cell_min, group_rows)
+  DevBuf f_cap, f_present, f_flag;   // kcc::FoldWork (kcc_spread_fold)
+  DevBuf f_ct, f_ce, f_gr, f_dom, f_el, f_skew;  // kcc_spread_fold staging
   DevBuf kb_counts, kb_tot, kb_sr, kb_sv;  // kcc::KeyedWork (bucketed keyed reduce)
   DevBuf kb_part, kb_arrive;               // one-sweep gather: part rows, arrivals (zeroed)
   DevBuf kb_esc_n, kb_esc_row, kb_esc_cpu, kb_esc_mem;
@@ -1025,7 +1029,9 @@ void kcc_destroy(kcc_ctx* ctx) {
                       &dv.q_omem,    &dv.q_pcpu,    &dv.q_pmem,
                       &dv.g_group,   &dv.g_count,   &dv.g_cursor,  &dv.g_total,   &dv.g_rec,
                       &dv.g_rg,      &dv.g_acc,     &dv.x_alloc,   &dv.x_used,    &dv.x_spec,
-                      &dv.x_rec};
+                      &dv.x_rec,     &dv.sp_qmin,   &dv.sp_cap,    &dv.sp_cmin,   &dv.sp_grows,
+                      &dv.f_cap,     &dv.f_present, &dv.f_flag,    &dv.f_ct,      &dv.f_ce,
+                      &dv.f_gr,      &dv.f_dom,     &dv.f_el,      &dv.f_skew};
     for (DevBuf* b : bufs)
       if (b->p) (void)hipFree(b->p);
     if (dv.stream) (void)hipStreamDestroy(dv.stream);
@@ -2080,6 +2086,264 @@ int kcc_fit_ext(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const 
   if (rc) return rc;
   KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
   KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
+  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
+  return KCC_OK;
+}
+
+}  // extern "C"
+
+
+// ---- spread constraints in the fit (kcc_spread.hip) -----------------------------------
+
+namespace {
+
+int fit_capped_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, const uint64_t* alloc_cpu,
+                   const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
+                   const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
+                   const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                   int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
+                   const int64_t* spec_mem, const int64_t* spec_x, int64_t* totals,
+                   int32_t* spec_err, const int64_t* node_cap, int64_t* cell_min,
+                   int64_t* group_rows, hipStream_t s) {
+  int rc = check_ext(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                     n_ext, alloc_x, used_x, group, n_groups, n_specs, spec_cpu, spec_mem, spec_x,
+                     totals, spec_err);
+  if (rc) return rc;
+  const size_t cells = (size_t)(n_groups * n_specs);
+  if (n_nodes == 0) {  // no rows: every cell empty, every group empty
+    if (n_specs > 0) {
+      KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * cells, s));
+      KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * cells, s));
+      if (cell_min) KCC_HIP(ctx, kcc::launch_fill_i64((int64_t)cells, INT64_MAX, cell_min, s));
+    }
+    if (group_rows) KCC_HIP(ctx, hipMemsetAsync(group_rows, 0, 8 * (size_t)n_groups, s));
+    return KCC_OK;
+  }
+  if (n_specs == 0) {  // no cells; the groups' rows are still counted
+    if (!group_rows) return KCC_OK;
+    KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)n_groups));
+    KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)n_groups));
+    KCC_HIP(ctx, ensure(dv.g_total, 16));
+    const kcc::GrpWork g{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor),
+                         as<uint32_t>(dv.g_total), nullptr, nullptr, nullptr};
+    KCC_HIP(ctx, kcc::launch_group_rows(n_nodes, n_groups, group, g, group_rows, s));
+    return KCC_OK;
+  }
+  if (kcc::grp_runs(n_nodes) * ((n_specs + kcc::GRP_PAIR_THREADS - 1) / kcc::GRP_PAIR_THREADS) >
+      0x7fffffff)
+    return fail(ctx, KCC_EINVAL, "n_nodes x n_specs beyond one launch (2^31 - 1 workgroups of 256 x 256 pairs)");
+  if (group) {
+    KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)n_groups));
+    KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)n_groups));
+    KCC_HIP(ctx, ensure(dv.g_total, 16));
+  }
+  KCC_HIP(ctx, ensure(dv.g_rec, sizeof(kcc::GrpRow) * (size_t)n_nodes));
+  KCC_HIP(ctx, ensure(dv.g_rg, 4 * (size_t)n_nodes));
+  KCC_HIP(ctx, ensure(dv.g_acc, 16 * cells));
+  KCC_HIP(ctx, ensure(dv.x_rec, sizeof(kcc::ExtCol) * (size_t)n_nodes * (size_t)n_ext));
+  if (cell_min) KCC_HIP(ctx, ensure(dv.sp_qmin, 8 * cells));
+  const kcc::ExtWork w{{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor), as<uint32_t>(dv.g_total),
+                        as<kcc::GrpRow>(dv.g_rec), as<int32_t>(dv.g_rg), as<int64_t>(dv.g_acc)},
+                       as<kcc::ExtCol>(dv.x_rec)};
+  KCC_HIP(ctx, kcc::launch_fit_capped(n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count,
+                                      used_cpu, used_mem, (int)n_ext, alloc_x, used_x, group,
+                                      n_groups, n_specs, spec_cpu, spec_mem, spec_x, node_cap, w,
+                                      as<unsigned long long>(dv.sp_qmin), totals, spec_err,
+                                      cell_min, group_rows, s));
+  return KCC_OK;
+}
+
+// Argument checks of both fold entry points.  *degenerate: nothing to launch.
+int check_fold(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs, const int64_t* cell_totals,
+               const int32_t* cell_err, const int32_t* domain_of, int64_t n_domains,
+               const int64_t* totals, const int32_t* spec_err, bool* degenerate) {
+  *degenerate = false;
+  if (n_groups < 0 || n_specs < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (n_specs > 0 && (!totals || !spec_err)) return fail(ctx, KCC_EINVAL, "NULL output");
+  if (n_groups == 0 || n_specs == 0) {
+    *degenerate = true;
+    return KCC_OK;
+  }
+  if (n_domains < 1) return fail(ctx, KCC_EINVAL, "n_domains must be at least 1");
+  if (!domain_of && n_domains != n_groups)
+    return fail(ctx, KCC_EINVAL, "domain_of is NULL: n_domains must equal n_groups");
+  if (n_specs > kcc::GRP_MAX_CELLS || n_groups > kcc::GRP_MAX_CELLS ||
+      n_domains > kcc::GRP_MAX_CELLS || n_groups * n_specs > kcc::GRP_MAX_CELLS ||
+      n_domains * n_specs > kcc::GRP_MAX_CELLS)
+    return fail(ctx, KCC_EINVAL, "too many cells: n_groups x n_specs and n_domains x n_specs must not exceed 2^28");
+  if (!cell_totals || !cell_err) return fail(ctx, KCC_EINVAL, "NULL cell array");
+  return KCC_OK;
+}
+
+int spread_fold_dev(kcc_ctx* ctx, Dev& dv, int64_t n_groups, int64_t n_specs,
+                    const int64_t* cell_totals, const int32_t* cell_err,
+                    const int64_t* group_rows, const int32_t* domain_of, int64_t n_domains,
+                    const uint8_t* eligible, const int64_t* max_skew, int64_t* totals,
+                    int32_t* spec_err, hipStream_t s) {
+  bool degenerate;
+  int rc = check_fold(ctx, n_groups, n_specs, cell_totals, cell_err, domain_of, n_domains, totals,
+                      spec_err, &degenerate);
+  if (rc) return rc;
+  if (degenerate) {
+    if (n_specs > 0) {
+      KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * (size_t)n_specs, s));
+      KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * (size_t)n_specs, s));
+    }
+    return KCC_OK;
+  }
+  const size_t dcells = (size_t)(n_domains * n_specs);
+  KCC_HIP(ctx, ensure(dv.f_cap, 8 * dcells));
+  KCC_HIP(ctx, ensure(dv.f_present, 4 * dcells));
+  KCC_HIP(ctx, ensure(dv.f_flag, 4 * (size_t)n_specs));
+  const kcc::FoldWork w{as<int64_t>(dv.f_cap), as<uint32_t>(dv.f_present), as<uint32_t>(dv.f_flag)};
+  KCC_HIP(ctx, kcc::launch_spread_fold(n_groups, n_specs, cell_totals, cell_err, group_rows,
+                                       domain_of, n_domains, eligible, max_skew, w, totals,
+                                       spec_err, s));
+  return KCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kcc_fit_capped_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                         const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
+                         const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                         const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                         const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                         int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                         const int64_t* d_spec_x, int64_t* d_totals, int32_t* d_spec_err,
+                         const int64_t* d_node_cap, int64_t* d_cell_min, int64_t* d_group_rows,
+                         void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  return fit_capped_dev(ctx, dv, n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count,
+                        d_used_cpu, d_used_mem, n_ext, d_alloc_x, d_used_x, d_group, n_groups,
+                        n_specs, d_spec_cpu, d_spec_mem, d_spec_x, d_totals, d_spec_err, d_node_cap,
+                        d_cell_min, d_group_rows, static_cast<hipStream_t>(stream));
+}
+
+int kcc_fit_capped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                   const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
+                   const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
+                   const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                   int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
+                   const int64_t* spec_mem, const int64_t* spec_x, int64_t* totals,
+                   int32_t* spec_err, const int64_t* node_cap, int64_t* cell_min,
+                   int64_t* group_rows) {
+  if (!ctx) return KCC_EINVAL;
+  int rc = check_ext(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                     n_ext, alloc_x, used_x, group, n_groups, n_specs, spec_cpu, spec_mem, spec_x,
+                     totals, spec_err);
+  if (rc) return rc;
+  const size_t cells = (size_t)(n_groups * n_specs);
+  if (n_nodes == 0) {
+    if (n_specs > 0) {
+      memset(totals, 0, 8 * cells);
+      memset(spec_err, 0, 4 * cells);
+      if (cell_min)
+        for (size_t k = 0; k < cells; ++k) cell_min[k] = INT64_MAX;
+    }
+    if (group_rows) memset(group_rows, 0, 8 * (size_t)n_groups);
+    return KCC_OK;
+  }
+  if (n_specs == 0 && !group_rows) return KCC_OK;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  if ((rc = h2d(ctx, dv, dv.alloc_cpu, alloc_cpu, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.alloc_mem, alloc_mem, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.alloc_pods, alloc_pods, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.pod_count, pod_count, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.used_cpu, used_cpu, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.used_mem, used_mem, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.x_alloc, alloc_x, n_ext * n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.x_used, used_x, n_ext * n_nodes))) return rc;
+  if (group && (rc = h2d(ctx, dv, dv.g_group, group, n_nodes))) return rc;
+  if ((rc = h2d(ctx, dv, dv.spec_cpu, spec_cpu, n_specs))) return rc;
+  if ((rc = h2d(ctx, dv, dv.spec_mem, spec_mem, n_specs))) return rc;
+  if ((rc = h2d(ctx, dv, dv.x_spec, spec_x, n_ext * n_specs))) return rc;
+  if (node_cap && (rc = h2d(ctx, dv, dv.sp_cap, node_cap, n_specs))) return rc;
+  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
+  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
+  if (cell_min) KCC_HIP(ctx, ensure(dv.sp_cmin, 8 * cells));
+  if (group_rows) KCC_HIP(ctx, ensure(dv.sp_grows, 8 * (size_t)n_groups));
+  rc = fit_capped_dev(ctx, dv, n_nodes, as<uint64_t>(dv.alloc_cpu), as<int64_t>(dv.alloc_mem),
+                      as<int64_t>(dv.alloc_pods), as<int64_t>(dv.pod_count),
+                      as<uint64_t>(dv.used_cpu), as<int64_t>(dv.used_mem), n_ext,
+                      as<int64_t>(dv.x_alloc), as<int64_t>(dv.x_used),
+                      group ? as<int32_t>(dv.g_group) : nullptr, n_groups, n_specs,
+                      as<uint64_t>(dv.spec_cpu), as<int64_t>(dv.spec_mem), as<int64_t>(dv.x_spec),
+                      as<int64_t>(dv.totals), as<int32_t>(dv.err),
+                      node_cap ? as<int64_t>(dv.sp_cap) : nullptr,
+                      cell_min ? as<int64_t>(dv.sp_cmin) : nullptr,
+                      group_rows ? as<int64_t>(dv.sp_grows) : nullptr, dv.stream);
+  if (rc) return rc;
+  if (n_specs > 0) {
+    KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
+    KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
+    if (cell_min)
+      KCC_HIP(ctx, hipMemcpyAsync(cell_min, dv.sp_cmin.p, 8 * cells, hipMemcpyDeviceToHost,
+                                  dv.stream));
+  }
+  if (group_rows)
+    KCC_HIP(ctx, hipMemcpyAsync(group_rows, dv.sp_grows.p, 8 * (size_t)n_groups,
+                                hipMemcpyDeviceToHost, dv.stream));
+  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
+  return KCC_OK;
+}
+
+int kcc_spread_fold_async(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs,
+                          const int64_t* d_cell_totals, const int32_t* d_cell_err,
+                          const int64_t* d_group_rows, const int32_t* d_domain_of,
+                          int64_t n_domains, const uint8_t* d_eligible, const int64_t* d_max_skew,
+                          int64_t* d_totals, int32_t* d_spec_err, void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  return spread_fold_dev(ctx, dv, n_groups, n_specs, d_cell_totals, d_cell_err, d_group_rows,
+                         d_domain_of, n_domains, d_eligible, d_max_skew, d_totals, d_spec_err,
+                         static_cast<hipStream_t>(stream));
+}
+
+int kcc_spread_fold(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs, const int64_t* cell_totals,
+                    const int32_t* cell_err, const int64_t* group_rows, const int32_t* domain_of,
+                    int64_t n_domains, const uint8_t* eligible, const int64_t* max_skew,
+                    int64_t* totals, int32_t* spec_err) {
+  if (!ctx) return KCC_EINVAL;
+  bool degenerate;
+  int rc = check_fold(ctx, n_groups, n_specs, cell_totals, cell_err, domain_of, n_domains, totals,
+                      spec_err, &degenerate);
+  if (rc) return rc;
+  if (degenerate) {
+    if (n_specs > 0) {
+      memset(totals, 0, 8 * (size_t)n_specs);
+      memset(spec_err, 0, 4 * (size_t)n_specs);
+    }
+    return KCC_OK;
+  }
+  const int64_t cells = n_groups * n_specs;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  if ((rc = h2d(ctx, dv, dv.f_ct, cell_totals, cells))) return rc;
+  if ((rc = h2d(ctx, dv, dv.f_ce, cell_err, cells))) return rc;
+  if (group_rows && (rc = h2d(ctx, dv, dv.f_gr, group_rows, n_groups))) return rc;
+  if (domain_of && (rc = h2d(ctx, dv, dv.f_dom, domain_of, n_groups))) return rc;
+  if (eligible && (rc = h2d(ctx, dv, dv.f_el, eligible, cells))) return rc;
+  if (max_skew && (rc = h2d(ctx, dv, dv.f_skew, max_skew, n_specs))) return rc;
+  KCC_HIP(ctx, ensure(dv.totals, 8 * (size_t)n_specs));
+  KCC_HIP(ctx, ensure(dv.err, 4 * (size_t)n_specs));
+  rc = spread_fold_dev(ctx, dv, n_groups, n_specs, as<int64_t>(dv.f_ct), as<int32_t>(dv.f_ce),
+                       group_rows ? as<int64_t>(dv.f_gr) : nullptr,
+                       domain_of ? as<int32_t>(dv.f_dom) : nullptr, n_domains,
+                       eligible ? as<uint8_t>(dv.f_el) : nullptr,
+                       max_skew ? as<int64_t>(dv.f_skew) : nullptr, as<int64_t>(dv.totals),
+                       as<int32_t>(dv.err), dv.stream);
+  if (rc) return rc;
+  KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * (size_t)n_specs, hipMemcpyDeviceToHost,
+                              dv.stream));
+  KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * (size_t)n_specs, hipMemcpyDeviceToHost,
+                              dv.stream));
   KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
   return KCC_OK;
 }

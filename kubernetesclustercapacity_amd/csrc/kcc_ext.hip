@@ -14,7 +14,9 @@
 //                       ext_scatter<R>  grp_scatter with the record widened by R ExtCol
 //   ext_pairs<R>        grp_pairs' plan: a wave holds 64 specs, walks GRP_RUN records staged
 //                       in LDS (read as broadcasts), per-lane int64 sums, 64-bit atomic adds
-//                       on a group change and at the end of the run
+//                       on a group change and at the end of the run (the body is
+//                       ext_pairs_body<R, false> in kcc_internal.h, shared with kcc_spread.hip's
+//                       cap_pairs<R>; its cap and minimum code does not exist here)
 //   grp_finalize        (kcc_groups.hip)
 // R is a template parameter: x[r] and the record's columns are indexed statically, no
 // kernel has a private segment.  LDS of ext_pairs<4>: 256 x (48 + 4 + 4 x 16) B = 29 KiB.
@@ -131,95 +133,32 @@ __global__ __launch_bounds__(GRP_PAIR_THREADS) void ext_pairs_kernel(
     const int64_t* __restrict__ spec_x, const GrpRow* __restrict__ rec,
     const ExtCol* __restrict__ xrec, const int32_t* __restrict__ rg, int64_t* __restrict__ acc,
     unsigned long long* __restrict__ cnt) {
-  constexpr int RR = R ? R : 1;
-  __shared__ GrpRow s_rec[GRP_RUN];
-  __shared__ ExtCol s_x[GRP_RUN * RR];
-  __shared__ int32_t s_rg[GRP_RUN];
-  const int64_t run = (int64_t)blockIdx.x / sblocks;
-  const int64_t sb = (int64_t)blockIdx.x - run * sblocks;
-  const int64_t M = total ? (int64_t)*total : n_rec;
-  const int64_t base = run * GRP_RUN;
-  if (base >= M) return;
-  const int nr = (int)(M - base < GRP_RUN ? M - base : GRP_RUN);
-  for (int j = threadIdx.x; j < nr; j += GRP_PAIR_THREADS) {
-    s_rec[j] = rec[base + j];
-    s_rg[j] = rg[base + j];
-  }
-  if constexpr (R > 0) {
-    for (int j = threadIdx.x; j < nr * R; j += GRP_PAIR_THREADS) s_x[j] = xrec[base * R + j];
-  }
-  __syncthreads();
+  ext_pairs_body<R, false>(total, n_rec, S, sblocks, spec_cpu, spec_mem, spec_x, rec, xrec, rg,
+                           acc, cnt, nullptr, nullptr);
+}
 
-  const int64_t s = sb * GRP_PAIR_THREADS + threadIdx.x;
-  const bool live = s < S;  // (a lane past S: c = m = 1, every x = 0 — a fast spec)
-  const uint64_t c = live ? spec_cpu[s] : 1;
-  const int64_t m = live ? spec_mem[s] : 1;
-  bool spec_fast = c >= 1 && c <= GRP_SPEC_MAX && m >= 1 && (uint64_t)m <= GRP_SPEC_MAX;
-  int64_t x[RR];
-  double xd[RR], rx[RR];
-#pragma unroll
-  for (int k = 0; k < R; ++k) {
-    x[k] = live ? spec_x[(int64_t)k * S + s] : 0;
-    spec_fast = spec_fast && (uint64_t)x[k] <= GRP_SPEC_MAX;  // 0 or [1, 2^52]
-    xd[k] = x[k] == 0 ? 1.0 : (double)x[k];  // a finite divisor for the unrequested lane
-    rx[k] = 1.0 / xd[k];                     // (used on the fast path only)
+// The launches ahead of the pair loop: acc / cnt zeroed, then the records.
+template <int R>
+hipError_t launch_records(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+                          const int64_t* alloc_pods, const int64_t* pod_count,
+                          const uint64_t* used_cpu, const int64_t* used_mem,
+                          const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                          int64_t G, int64_t S, const ExtWork& w, hipStream_t s) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(w.g.acc, 0, 16 * (size_t)(G * S), s)) != hipSuccess) return e;
+  if (group) {
+    const int64_t sort_grid = (n + GRP_SORT_THREADS - 1) / GRP_SORT_THREADS;
+    const int lds = G <= GRP_LDS_GROUPS ? 1 : 0;
+    if ((e = launch_grp_count_scan(n, G, group, w.g, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(ext_scatter_kernel<R>, dim3((unsigned)sort_grid), dim3(GRP_SORT_THREADS), 0,
+                       s, n, G, group, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
+                       used_mem, alloc_x, used_x, w.g.cursor, w.g.rec, w.xrec, w.g.rg, lds);
+  } else {
+    hipLaunchKernelGGL(ext_rows_kernel<R>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n,
+                       alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem, alloc_x,
+                       used_x, w.g.rec, w.xrec, w.g.rg);
   }
-  const bool wave_fast = __all(spec_fast);
-  const double cd = (double)c, md = (double)m;
-  const double rc = 1.0 / cd, rm = 1.0 / md;  // (used on the fast path only: c, m >= 1 there)
-
-  int64_t sum = 0;
-  unsigned long long z = 0;
-  int gcur = __builtin_amdgcn_readfirstlane(s_rg[0]) & (GRP_ROW_FAST - 1);
-  for (int j = 0; j < nr; ++j) {
-    const int meta = __builtin_amdgcn_readfirstlane(s_rg[j]);
-    const int g = meta & (GRP_ROW_FAST - 1);
-    if (g != gcur) {  // wave-uniform
-      grp_flush(acc, cnt, (int64_t)gcur * S + s, live, sum, z);
-      sum = 0;
-      z = 0;
-      gcur = g;
-    }
-    const GrpRow r = s_rec[j];
-    int64_t q;
-    if (wave_fast && (meta & GRP_ROW_FAST)) {  // wave-uniform
-      const double tc = grp_div(r.fcd, cd, rc);
-      const double tm = grp_div(r.fmd, md, rm);
-      double t = tc <= tm ? tc : tm;  // findMin (CC:133)
-#pragma unroll
-      for (int k = 0; k < R; ++k) {
-        const double tx = grp_div(s_x[j * RR + k].fxd, xd[k], rx[k]);
-        t = (x[k] != 0 && tx < t) ? tx : t;  // the unrequested lane's quotient is never used
-      }
-      q = (int64_t)(int32_t)t;  // <= free CPU < 2^31
-    } else {
-      int64_t qc = 0, qm = 0;
-      bool dz = false;
-      if (r.fc != 0) {  // CC:119-124 (uint64 division, int() reinterprets)
-        if (c == 0) dz = true;
-        else qc = (int64_t)(r.fc / c);
-      }
-      if (r.fm != 0) {  // CC:125-130
-        if (m == 0) dz = true;
-        else if (m == -1) qm = (int64_t)(0ull - (uint64_t)r.fm);  // MinInt64 / -1 == MinInt64
-        else qm = r.fm / m;
-      }
-      q = qc <= qm ? qc : qm;  // findMin, CC:133
-#pragma unroll
-      for (int k = 0; k < R; ++k) {
-        const int64_t fx = s_x[j * RR + k].fx;
-        if (x[k] != 0) {  // zero: not requested
-          int64_t qx = 0;
-          if (fx != 0) qx = x[k] == -1 ? (int64_t)(0ull - (uint64_t)fx) : fx / x[k];
-          q = q <= qx ? q : qx;
-        }
-      }
-      z += dz ? 1u : 0u;
-    }
-    if (q >= r.P) q = r.cl;  // CC:134-136, after all the mins
-    sum = (int64_t)((uint64_t)sum + (uint64_t)q);
-  }
-  grp_flush(acc, cnt, (int64_t)gcur * S + s, live, sum, z);
+  return hipGetLastError();
 }
 
 template <int R>
@@ -233,26 +172,22 @@ hipError_t launch_ext(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc
   const int64_t sblocks = (S + GRP_PAIR_THREADS - 1) / GRP_PAIR_THREADS;
   const int64_t pair_grid = grp_runs(n) * sblocks;
   hipError_t e;
-  if ((e = hipMemsetAsync(w.g.acc, 0, 16 * (size_t)cells, s)) != hipSuccess) return e;
+  if ((e = launch_records<R>(n, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                             alloc_x, used_x, group, G, S, w, s)) != hipSuccess)
+    return e;
   int64_t* acc = w.g.acc;
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(w.g.acc + cells);
-  if (group) {
-    const int64_t sort_grid = (n + GRP_SORT_THREADS - 1) / GRP_SORT_THREADS;
-    const int lds = G <= GRP_LDS_GROUPS ? 1 : 0;
-    if ((e = launch_grp_count_scan(n, G, group, w.g, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(ext_scatter_kernel<R>, dim3((unsigned)sort_grid), dim3(GRP_SORT_THREADS), 0,
-                       s, n, G, group, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
-                       used_mem, alloc_x, used_x, w.g.cursor, w.g.rec, w.xrec, w.g.rg, lds);
-  } else {
-    hipLaunchKernelGGL(ext_rows_kernel<R>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n,
-                       alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem, alloc_x,
-                       used_x, w.g.rec, w.xrec, w.g.rg);
-  }
   hipLaunchKernelGGL(ext_pairs_kernel<R>, dim3((unsigned)pair_grid), dim3(GRP_PAIR_THREADS), 0, s,
                      group ? w.g.total : (const uint32_t*)nullptr, n, S, sblocks, spec_cpu,
                      spec_mem, spec_x, w.g.rec, w.xrec, w.g.rg, acc, cnt);
   if ((e = launch_grp_finalize(cells, acc, cnt, totals, spec_err, s)) != hipSuccess) return e;
   return hipGetLastError();
+}
+
+bool ext_sizes_ok(int64_t n, int R, const int32_t* group, int64_t G, int64_t S) {
+  if (n <= 0 || S <= 0 || G <= 0 || R < 0 || R > EXT_MAX || (!group && G != 1)) return false;
+  const int64_t sblocks = (S + GRP_PAIR_THREADS - 1) / GRP_PAIR_THREADS;
+  return G * S <= GRP_MAX_CELLS && n <= GRP_MAX_NODES && grp_runs(n) * sblocks <= 0x7fffffff;
 }
 
 }  // namespace
@@ -264,16 +199,33 @@ hipError_t launch_fit_ext(int64_t n, const uint64_t* alloc_cpu, const int64_t* a
                           int64_t G, int64_t S, const uint64_t* spec_cpu, const int64_t* spec_mem,
                           const int64_t* spec_x, const ExtWork& w, int64_t* totals,
                           int32_t* spec_err, hipStream_t s) {
-  if (n <= 0 || S <= 0 || G <= 0 || R < 0 || R > EXT_MAX || (!group && G != 1))
-    return hipErrorInvalidValue;
-  const int64_t sblocks = (S + GRP_PAIR_THREADS - 1) / GRP_PAIR_THREADS;
-  if (G * S > GRP_MAX_CELLS || n > GRP_MAX_NODES || grp_runs(n) * sblocks > 0x7fffffff)
-    return hipErrorInvalidValue;
+  if (!ext_sizes_ok(n, R, group, G, S)) return hipErrorInvalidValue;
 #define KCC_EXT_CASE(r)                                                                         \
   case r:                                                                                       \
     return launch_ext<r>(n, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,    \
                          alloc_x, used_x, group, G, S, spec_cpu, spec_mem, spec_x, w, totals,   \
                          spec_err, s)
+  switch (R) {
+    KCC_EXT_CASE(0);
+    KCC_EXT_CASE(1);
+    KCC_EXT_CASE(2);
+    KCC_EXT_CASE(3);
+    KCC_EXT_CASE(4);
+  }
+#undef KCC_EXT_CASE
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_ext_records(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+                              const int64_t* alloc_pods, const int64_t* pod_count,
+                              const uint64_t* used_cpu, const int64_t* used_mem, int R,
+                              const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                              int64_t G, int64_t S, const ExtWork& w, hipStream_t s) {
+  if (!ext_sizes_ok(n, R, group, G, S)) return hipErrorInvalidValue;
+#define KCC_EXT_CASE(r)                                                                         \
+  case r:                                                                                       \
+    return launch_records<r>(n, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,          \
+                             used_mem, alloc_x, used_x, group, G, S, w, s)
   switch (R) {
     KCC_EXT_CASE(0);
     KCC_EXT_CASE(1);

@@ -664,6 +664,170 @@ hipError_t launch_fit_ext(int64_t n, const uint64_t* alloc_cpu, const int64_t* a
                           int64_t G, int64_t S, const uint64_t* spec_cpu, const int64_t* spec_mem,
                           const int64_t* spec_x, const ExtWork& w, int64_t* totals,
                           int32_t* spec_err, hipStream_t s);
+// The launches of launch_fit_ext ahead of its pair loop: acc / cnt [2 G S] zeroed, then the
+// records (hist, scan and scatter with group ids; one row pass without).  Same arguments.
+hipError_t launch_ext_records(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+                              const int64_t* alloc_pods, const int64_t* pod_count,
+                              const uint64_t* used_cpu, const int64_t* used_mem, int R,
+                              const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                              int64_t G, int64_t S, const ExtWork& w, hipStream_t s);
+
+#if defined(__HIPCC__)
+constexpr unsigned long long SPREAD_SIGN = 1ull << 63;  // qmin[] cells: q ^ SPREAD_SIGN, unsigned order
+
+// The pair loop of ext_pairs<R> (kcc_ext.hip) and of cap_pairs<R> (kcc_spread.hip): one body,
+// so the two cannot drift apart.  SPREAD adds, after the one conversion and after the
+// pod-slot clamp, the per-lane minimum of q and the per-node cap (integer compare-and-
+// selects), and flushes the minimum with a 64-bit atomic min where grp_flush runs; without
+// SPREAD none of that code exists.  total == nullptr: the n_rec records of the ungrouped
+// pass; else *total (the rows with a valid group id, from grp_scan).
+template <int R, bool SPREAD>
+__device__ inline void ext_pairs_body(
+    const uint32_t* __restrict__ total, int64_t n_rec, int64_t S, int64_t sblocks,
+    const uint64_t* __restrict__ spec_cpu, const int64_t* __restrict__ spec_mem,
+    const int64_t* __restrict__ spec_x, const GrpRow* __restrict__ rec,
+    const ExtCol* __restrict__ xrec, const int32_t* __restrict__ rg, int64_t* __restrict__ acc,
+    unsigned long long* __restrict__ cnt, const int64_t* __restrict__ node_cap,
+    unsigned long long* __restrict__ qmin) {
+  constexpr int RR = R ? R : 1;
+  __shared__ GrpRow s_rec[GRP_RUN];
+  __shared__ ExtCol s_x[GRP_RUN * RR];
+  __shared__ int32_t s_rg[GRP_RUN];
+  const int64_t run = (int64_t)blockIdx.x / sblocks;
+  const int64_t sb = (int64_t)blockIdx.x - run * sblocks;
+  const int64_t M = total ? (int64_t)*total : n_rec;
+  const int64_t base = run * GRP_RUN;
+  if (base >= M) return;
+  const int nr = (int)(M - base < GRP_RUN ? M - base : GRP_RUN);
+  for (int j = threadIdx.x; j < nr; j += GRP_PAIR_THREADS) {
+    s_rec[j] = rec[base + j];
+    s_rg[j] = rg[base + j];
+  }
+  if constexpr (R > 0) {
+    for (int j = threadIdx.x; j < nr * R; j += GRP_PAIR_THREADS) s_x[j] = xrec[base * R + j];
+  }
+  __syncthreads();
+
+  const int64_t s = sb * GRP_PAIR_THREADS + threadIdx.x;
+  const bool live = s < S;  // (a lane past S: c = m = 1, every x = 0 — a fast spec)
+  const uint64_t c = live ? spec_cpu[s] : 1;
+  const int64_t m = live ? spec_mem[s] : 1;
+  bool spec_fast = c >= 1 && c <= GRP_SPEC_MAX && m >= 1 && (uint64_t)m <= GRP_SPEC_MAX;
+  int64_t x[RR];
+  double xd[RR], rx[RR];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    x[k] = live ? spec_x[(int64_t)k * S + s] : 0;
+    spec_fast = spec_fast && (uint64_t)x[k] <= GRP_SPEC_MAX;  // 0 or [1, 2^52]
+    xd[k] = x[k] == 0 ? 1.0 : (double)x[k];  // a finite divisor for the unrequested lane
+    rx[k] = 1.0 / xd[k];                     // (used on the fast path only)
+  }
+  const bool wave_fast = __all(spec_fast);
+  const double cd = (double)c, md = (double)m;
+  const double rc = 1.0 / cd, rm = 1.0 / md;  // (used on the fast path only: c, m >= 1 there)
+  [[maybe_unused]] int64_t capv = INT64_MAX;  // SPREAD: no cap (NULL or <= 0) is a cap nothing exceeds
+  if constexpr (SPREAD) {
+    const int64_t k = (node_cap && live) ? node_cap[s] : 0;
+    capv = k > 0 ? k : INT64_MAX;
+  }
+
+  int64_t sum = 0;
+  [[maybe_unused]] int64_t mn = INT64_MAX;
+  unsigned long long z = 0;
+  int gcur = __builtin_amdgcn_readfirstlane(s_rg[0]) & (GRP_ROW_FAST - 1);
+  for (int j = 0; j < nr; ++j) {
+    const int meta = __builtin_amdgcn_readfirstlane(s_rg[j]);
+    const int g = meta & (GRP_ROW_FAST - 1);
+    if (g != gcur) {  // wave-uniform
+      grp_flush(acc, cnt, (int64_t)gcur * S + s, live, sum, z);
+      if constexpr (SPREAD) {
+        if (qmin && live) atomicMin(qmin + (int64_t)gcur * S + s, (unsigned long long)mn ^ SPREAD_SIGN);
+        mn = INT64_MAX;
+      }
+      sum = 0;
+      z = 0;
+      gcur = g;
+    }
+    const GrpRow r = s_rec[j];
+    int64_t q;
+    if (wave_fast && (meta & GRP_ROW_FAST)) {  // wave-uniform
+      const double tc = grp_div(r.fcd, cd, rc);
+      const double tm = grp_div(r.fmd, md, rm);
+      double t = tc <= tm ? tc : tm;  // findMin (CC:133)
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const double tx = grp_div(s_x[j * RR + k].fxd, xd[k], rx[k]);
+        t = (x[k] != 0 && tx < t) ? tx : t;  // the unrequested lane's quotient is never used
+      }
+      q = (int64_t)(int32_t)t;  // <= free CPU < 2^31
+    } else {
+      int64_t qc = 0, qm = 0;
+      bool dz = false;
+      if (r.fc != 0) {  // CC:119-124 (uint64 division, int() reinterprets)
+        if (c == 0) dz = true;
+        else qc = (int64_t)(r.fc / c);
+      }
+      if (r.fm != 0) {  // CC:125-130
+        if (m == 0) dz = true;
+        else if (m == -1) qm = (int64_t)(0ull - (uint64_t)r.fm);  // MinInt64 / -1 == MinInt64
+        else qm = r.fm / m;
+      }
+      q = qc <= qm ? qc : qm;  // findMin, CC:133
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int64_t fx = s_x[j * RR + k].fx;
+        if (x[k] != 0) {  // zero: not requested
+          int64_t qx = 0;
+          if (fx != 0) qx = x[k] == -1 ? (int64_t)(0ull - (uint64_t)fx) : fx / x[k];
+          q = q <= qx ? q : qx;
+        }
+      }
+      z += dz ? 1u : 0u;
+    }
+    if (q >= r.P) q = r.cl;  // CC:134-136, after all the mins
+    if constexpr (SPREAD) {
+      mn = q < mn ? q : mn;      // the cell's minimum: before the cap
+      q = q > capv ? capv : q;   // at most node_cap[s] on one node: after the clamp
+    }
+    sum = (int64_t)((uint64_t)sum + (uint64_t)q);
+  }
+  grp_flush(acc, cnt, (int64_t)gcur * S + s, live, sum, z);
+  if constexpr (SPREAD) {
+    if (qmin && live) atomicMin(qmin + (int64_t)gcur * S + s, (unsigned long long)mn ^ SPREAD_SIGN);
+  }
+}
+#endif
+
+// ---- spread constraints in the fit (kcc_spread.hip) ----------------
+// kcc_fit_capped: launch_fit_ext's arguments, then node_cap [S] (nullable; <= 0: no cap),
+// qmin [G S] (workspace of cell_min; unused when cell_min is nullptr), and the nullable
+// outputs cell_min [G S] and group_rows [G].  node_cap and cell_min both nullptr: the
+// launches of launch_fit_ext themselves.
+hipError_t launch_fit_capped(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+                             const int64_t* alloc_pods, const int64_t* pod_count,
+                             const uint64_t* used_cpu, const int64_t* used_mem, int R,
+                             const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                             int64_t G, int64_t S, const uint64_t* spec_cpu,
+                             const int64_t* spec_mem, const int64_t* spec_x,
+                             const int64_t* node_cap, const ExtWork& w, unsigned long long* qmin,
+                             int64_t* totals, int32_t* spec_err, int64_t* cell_min,
+                             int64_t* group_rows, hipStream_t s);
+// group_rows alone (no specs): grp_hist's counts widened; group == nullptr: out[0] = n.
+hipError_t launch_group_rows(int64_t n, int64_t G, const int32_t* group, const GrpWork& w,
+                             int64_t* group_rows, hipStream_t s);
+// out[0 .. cells) = v (the cells of cell_min when there are no rows).
+hipError_t launch_fill_i64(int64_t cells, int64_t v, int64_t* out, hipStream_t s);
+// kcc_spread_fold: G x S cells to one total per spec.  G, S, D >= 1; G S, D S <= 2^28.
+struct FoldWork {
+  int64_t* cap;       // [D S] wrapping sum of the live cells of domain d, spec s
+  uint32_t* present;  // [D S] nonzero: domain d has a live group for spec s
+  uint32_t* flag;     // [S] nonzero: a live cell of spec s is flagged
+};
+hipError_t launch_spread_fold(int64_t G, int64_t S, const int64_t* cell_totals,
+                              const int32_t* cell_err, const int64_t* group_rows,
+                              const int32_t* domain_of, int64_t D, const uint8_t* eligible,
+                              const int64_t* max_skew, const FoldWork& w, int64_t* totals,
+                              int32_t* spec_err, hipStream_t s);
 
 // ---- opt-in scheduler request model (kcc_pods.hip) ---------------
 hipError_t launch_pod_requests(int64_t n_pods, int64_t n_cont, int64_t n_init,

@@ -226,6 +226,169 @@ class CapacityEngine:
             int(n_groups), s, _dp(spec_cpu), _dp(spec_mem), _dp(spec_x), _dp(totals),
             _dp(spec_err), _stream(stream)))
 
+    # -- spread constraints (opt-in; include/kcc.h) -----------------
+    def fit_capped(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                   alloc_x, used_x, spec_cpu, spec_mem, spec_x, group=None, n_groups=1,
+                   node_cap=None, want_min=True, want_rows=True):
+        """fit_ext with a per-spec cap on one node's count (node_cap int64 [S]; <= 0 or None:
+        no cap; "at most k per node", applied after the pod-slot clamp), the minimum of q
+        over each cell's rows before the cap (cell_min) and the rows of each group
+        (group_rows).  Opt-in, not the reference's arithmetic; with node_cap None and
+        want_min / want_rows False it is fit_ext bit for bit.  alloc_x / used_x / spec_x may
+        be None (no extra resource).  Returns (totals int64, err int32, cell_min int64 or
+        None, group_rows int64 [n_groups] or None); the first three are [S] without group ids
+        and [n_groups, S] with them.  A flagged cell has cell_min 0, a cell with no rows
+        INT64_MAX."""
+        a = [_arr(alloc_cpu, np.uint64), _arr(alloc_mem, np.int64), _arr(alloc_pods, np.int64),
+             _arr(pod_count, np.int64), _arr(used_cpu, np.uint64), _arr(used_mem, np.int64)]
+        n = a[0].size
+        if any(x.size != n for x in a):
+            raise ValueError("node arrays differ in length")
+        sc, sm = _arr(spec_cpu, np.uint64), _arr(spec_mem, np.int64)
+        if sc.size != sm.size:
+            raise ValueError("spec arrays differ in length")
+        S = sc.size
+        ax = _arr(np.zeros((0, n)) if alloc_x is None else alloc_x, np.int64)
+        ux = _arr(np.zeros((0, n)) if used_x is None else used_x, np.int64)
+        sx = _arr(np.zeros((0, S)) if spec_x is None else spec_x, np.int64)
+        if ax.ndim != 2 or ux.shape != ax.shape or ax.shape[1] != n:
+            raise ValueError("alloc_x and used_x must both be [R, N]")
+        R = ax.shape[0]
+        if sx.shape != (R, S):
+            raise ValueError("spec_x must be [R, S]")
+        G = int(n_groups)
+        if group is not None:
+            group = _key32(group)
+            if group.size != n:
+                raise ValueError("node arrays differ in length")
+        cap = None if node_cap is None else _arr(node_cap, np.int64)
+        if cap is not None and cap.shape != (S,):
+            raise ValueError("node_cap must be [S]")
+        totals = np.zeros((max(G, 0), S), np.int64)
+        err = np.zeros((max(G, 0), S), np.int32)
+        cmin = np.zeros((max(G, 0), S), np.int64) if want_min else None
+        grows = np.zeros(max(G, 0), np.int64) if want_rows else None
+        self._check(self._lib.kcc_fit_capped(self._h, n, *[_p(x) for x in a], R, _p(ax), _p(ux),
+                                             _p(group), G, S, _p(sc), _p(sm), _p(sx),
+                                             _p(totals), _p(err), _p(cap), _p(cmin), _p(grows)))
+        if group is None:
+            return totals[0], err[0], None if cmin is None else cmin[0], grows
+        return totals, err, cmin, grows
+
+    def fit_capped_async(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                         n_ext, alloc_x, used_x, group, n_groups, spec_cpu, spec_mem, spec_x,
+                         totals, spec_err, node_cap=None, cell_min=None, group_rows=None,
+                         stream=None):
+        """Device form of fit_capped (torch tensors on the engine's device, as
+        fit_ext_async's; node_cap int64 [S], cell_min int64 of n_groups * S elements,
+        group_rows int64 [n_groups]).  The arguments go to the C-ABI as they are (None:
+        NULL), which validates them."""
+        n = 0 if alloc_cpu is None else alloc_cpu.numel()
+        s = 0 if spec_cpu is None else spec_cpu.numel()
+        self._check(self._lib.kcc_fit_capped_async(
+            self._h, n, _dp(alloc_cpu), _dp(alloc_mem), _dp(alloc_pods), _dp(pod_count),
+            _dp(used_cpu), _dp(used_mem), int(n_ext), _dp(alloc_x), _dp(used_x), _dp(group),
+            int(n_groups), s, _dp(spec_cpu), _dp(spec_mem), _dp(spec_x), _dp(totals),
+            _dp(spec_err), _dp(node_cap), _dp(cell_min), _dp(group_rows), _stream(stream)))
+
+    def spread_fold(self, cell_totals, cell_err, group_rows=None, domain_of=None,
+                    n_domains=None, eligible=None, max_skew=None):
+        """The G x S cells to one total per spec under a maxSkew over topology domains
+        (topologySpreadConstraints, DoNotSchedule; opt-in).  domain_of int32 [G] maps groups
+        to domains, many to one (None: each group its own domain); a group is live when
+        group_rows[g] > 0 (None: all), eligible (bool [G, S] or [G]; None: all) and its
+        domain id lies in [0, n_domains).  max_skew int64 [S] (None or <= 0:
+        unconstrained, the sum of the live cells — select_groups' answer).  Returns
+        (totals int64[S], err int32[S]); err[s] = 1 (totals 0) when a live cell is flagged."""
+        t = _arr(cell_totals, np.int64)
+        e = _arr(cell_err, np.int32)
+        if t.ndim != 2 or e.shape != t.shape:
+            raise ValueError("cell_totals and cell_err must both be [G, S]")
+        G, S = t.shape
+        gr = None if group_rows is None else _arr(group_rows, np.int64)
+        dom = None if domain_of is None else _key32(domain_of)
+        for v in (gr, dom):
+            if v is not None and v.shape != (G,):
+                raise ValueError("group_rows and domain_of must be [G]")
+        if n_domains is None:
+            n_domains = G if dom is None else max(int(dom.max(initial=0)) + 1, 1)
+        el = None
+        if eligible is not None:
+            m = np.asarray(eligible, bool)
+            if m.shape == (G,):
+                m = np.broadcast_to(m[:, None], t.shape)
+            if m.shape != t.shape:
+                raise ValueError("eligible must be [G, S] or [G]")
+            el = _arr(m, np.uint8)
+        sk = None if max_skew is None else _arr(max_skew, np.int64)
+        if sk is not None and sk.shape != (S,):
+            raise ValueError("max_skew must be [S]")
+        totals = np.zeros(S, np.int64)
+        err = np.zeros(S, np.int32)
+        self._check(self._lib.kcc_spread_fold(self._h, G, S, _p(t), _p(e), _p(gr), _p(dom),
+                                              int(n_domains), _p(el), _p(sk), _p(totals),
+                                              _p(err)))
+        return totals, err
+
+    def spread_fold_async(self, n_groups, n_specs, cell_totals, cell_err, group_rows, domain_of,
+                          n_domains, eligible, max_skew, totals, spec_err, stream=None):
+        """Device form of spread_fold (torch tensors: cells int64 / int32 of G * S elements,
+        group_rows int64 [G], domain_of int32 [G], eligible uint8 of G * S, max_skew int64
+        [S], totals int64 / spec_err int32 [S]; None: NULL).  No readback: it can follow
+        fit_capped_async on one stream, or in one captured graph."""
+        self._check(self._lib.kcc_spread_fold_async(
+            self._h, int(n_groups), int(n_specs), _dp(cell_totals), _dp(cell_err),
+            _dp(group_rows), _dp(domain_of), int(n_domains), _dp(eligible), _dp(max_skew),
+            _dp(totals), _dp(spec_err), _stream(stream)))
+
+    def fit_spread(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                   alloc_x, used_x, spec_cpu, spec_mem, spec_x, group=None, n_groups=1,
+                   node_cap=None, zone_of=None, max_skew=None, eligible=None,
+                   host_max_skew=None, n_zones=None):
+        """Replicas per spec under spread constraints, in one call: fit_capped, then
+        spread_fold with zone_of as the groups' domains.
+          node_cap       int64 [S]: at most this many on one node (<= 0: no cap)
+          zone_of        int32 [G]: the zone of each group (None: each group its own domain)
+          max_skew       int64 [S]: maxSkew over the zones (None or <= 0: unconstrained)
+          eligible       bool [G, S] or [G]: the groups a spec's selector admits
+          host_max_skew  int64 [S]: maxSkew with topologyKey kubernetes.io/hostname
+          n_zones        zones (None: the largest id in zone_of + 1); ids outside are skipped
+        host_max_skew takes two pair passes: the first gives cell_min; m[s] is its minimum
+        over the live eligible groups (a node over its pod limit counts as holding 0), and
+        the second pass caps a node at max(m[s], 0) + host_max_skew[s] (saturating), combined
+        with node_cap by min.  That minimum over G x S numbers is the only host arithmetic
+        here, like select_groups'.  Returns (totals int64[S], err int32[S])."""
+        rows6 = (alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem)
+        S = np.asarray(spec_cpu).size
+        G = int(n_groups)
+        cap = None if node_cap is None else _arr(node_cap, np.int64)
+        two = host_max_skew is not None
+        t, e, cmin, grows = self.fit_capped(*rows6, alloc_x, used_x, spec_cpu, spec_mem, spec_x,
+                                            group, G, cap, want_min=two)
+        if two:
+            hk = _arr(host_max_skew, np.int64)
+            if hk.shape != (S,):
+                raise ValueError("host_max_skew must be [S]")
+            live = np.broadcast_to((grows > 0)[:, None], (G, S))
+            if zone_of is not None:
+                z = np.asarray(zone_of, np.int64)
+                nz = int(n_zones) if n_zones is not None else max(int(z.max(initial=0)) + 1, 1)
+                live = live & ((z >= 0) & (z < nz))[:, None]
+            if eligible is not None:
+                m = np.asarray(eligible, bool)
+                live = live & (m[:, None] if m.ndim == 1 else m)
+            big = np.iinfo(np.int64).max
+            m = np.where(live, cmin.reshape(G, S), big).min(axis=0, initial=big)
+            m = np.maximum(m, 0)
+            hcap = np.where(hk > big - m, big, m + np.minimum(hk, big - m))  # saturating
+            cap2 = np.where(hk > 0, hcap, 0)
+            if cap is not None:
+                cap2 = np.where(cap > 0, np.where(cap2 > 0, np.minimum(cap, cap2), cap), cap2)
+            t, e, _, grows = self.fit_capped(*rows6, alloc_x, used_x, spec_cpu, spec_mem, spec_x,
+                                             group, G, cap2, want_min=False)
+        return self.spread_fold(t.reshape(G, S), e.reshape(G, S), grows, zone_of, n_zones,
+                                eligible, max_skew)
+
     def capacity(self, node_ptr, cpu_req, mem_req, alloc_cpu, alloc_mem, alloc_pods, pod_count,
                  spec_cpu, spec_mem):
         """Fused (a)+(b) on host arrays.  Returns (totals, spec_err)."""
