@@ -6,7 +6,7 @@
 // on the GPU through the C-ABI (kcc_capacity).  Additions: -specs <file> (a batch of
 // what-if specs, one "cpuRequests memRequests replicas" per line), -v (per-node
 // report of CC:107-117/137), -device/-gpus, -byPool (the totals per node pool, from
-// kcc_fit_grouped: "Pool <name> : <total>" lines after the reference's output),
+// the grouped fit: "Pool <name> : <total>" lines after the reference's output),
 // -extRequests name=amount[,name=amount...] (the pod also requests extended resources —
 // device-plugin GPUs, ephemeral-storage, hugepages — which the cluster file gives per node
 // as `resource` lines and per container as `request` lines; in a -specs file trailing
@@ -549,11 +549,10 @@ int main(int argc, char** argv) {
     zerr.resize((size_t)(Z * S));
     zrows.resize((size_t)Z);
     rc = kcc_fit_capped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
-                        in.pod_count.data(), uc.data(), um.data(), useExt ? ext.R() : 0,
-                        useExt ? ext.alloc_x.data() : nullptr, useExt ? ext.used_x.data() : nullptr,
-                        byZone ? group.data() : nullptr, Z, S, sc.data(), sm.data(),
-                        useExt ? ext.spec_x.data() : nullptr, ztot.data(), zerr.data(),
-                        caps.data(), nullptr, zrows.data());
+                        in.pod_count.data(), uc.data(), um.data(), ext.R(), ext.alloc_x.data(),
+                        ext.used_x.data(), byZone ? group.data() : nullptr, Z, S, sc.data(),
+                        sm.data(), ext.spec_x.data(), ztot.data(), zerr.data(), caps.data(),
+                        nullptr, zrows.data());  // (without extended resources ext is empty: R 0)
     if (rc) return fail(ctx, rc);
     const std::vector<int64_t> skew(specs.size(), byZone ? maxSkew : 0);
     rc = kcc_spread_fold(ctx, Z, S, ztot.data(), zerr.data(), zrows.data(), nullptr, Z, nullptr,
@@ -608,24 +607,13 @@ int main(int argc, char** argv) {
     }
     ptot.resize(pools.size() * specs.size());
     perr.resize(pools.size() * specs.size());
-    if (maxPerNode > 0)  // the pools under the per-node cap
-      rc = kcc_fit_capped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
-                          in.pod_count.data(), uc.data(), um.data(), useExt ? ext.R() : 0,
-                          useExt ? ext.alloc_x.data() : nullptr,
-                          useExt ? ext.used_x.data() : nullptr, group.data(),
-                          (int64_t)pools.size(), S, sc.data(), sm.data(),
-                          useExt ? ext.spec_x.data() : nullptr, ptot.data(), perr.data(),
-                          caps.data(), nullptr, nullptr);
-    else if (useExt)
-      rc = kcc_fit_ext(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
-                       in.pod_count.data(), uc.data(), um.data(), ext.R(), ext.alloc_x.data(),
-                       ext.used_x.data(), group.data(), (int64_t)pools.size(), S, sc.data(),
-                       sm.data(), ext.spec_x.data(), ptot.data(), perr.data());
-    else
-      rc = kcc_fit_grouped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
-                           in.pod_count.data(), uc.data(), um.data(), group.data(),
-                           (int64_t)pools.size(), (int64_t)specs.size(), sc.data(), sm.data(),
-                           ptot.data(), perr.data());
+    // one call: the pools under the per-node cap if there is one, with the extended
+    // resources if there are any (without them ext is empty: R 0) — else the grouped fit
+    rc = kcc_fit_capped(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                        in.pod_count.data(), uc.data(), um.data(), ext.R(), ext.alloc_x.data(),
+                        ext.used_x.data(), group.data(), (int64_t)pools.size(), S, sc.data(),
+                        sm.data(), ext.spec_x.data(), ptot.data(), perr.data(),
+                        maxPerNode > 0 ? caps.data() : nullptr, nullptr, nullptr);
     if (rc) return fail(ctx, rc);
   }
   auto printPools = [&](size_t s) {

@@ -1836,60 +1836,151 @@ extern "C" int kcc_fit_rows(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc
 }
 
 
-// ---- grouped fit: per node-group x spec totals (kcc_groups.hip) ------------------------
+// ---- the cell fits: per node-group x spec totals (kcc_ext.hip, kcc_spread.hip) ---------
+// kcc_fit_grouped, kcc_fit_ext and kcc_fit_capped are one path.  The extended fit is the
+// capped one without node_cap, cell_min and group_rows; the grouped fit is the extended one
+// with n_ext = 0 and group ids it insists on (need_group).
 
 namespace {
 
-// Argument checks of both grouped entry points (host or device pointers alike).
-int check_grouped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
-                  const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
-                  const uint64_t* used_cpu, const int64_t* used_mem, const int32_t* group,
-                  int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
-                  const int64_t* spec_mem, const int64_t* totals, const int32_t* spec_err) {
-  if (n_nodes < 0 || n_specs < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  if (n_groups < 1) return fail(ctx, KCC_EINVAL, "n_groups must be at least 1");
-  if (n_nodes > kcc::GRP_MAX_NODES) return fail(ctx, KCC_EINVAL, "too many nodes (max 2^31 - 4096)");
-  if (n_specs > kcc::GRP_MAX_CELLS || n_groups > kcc::GRP_MAX_CELLS ||
-      n_groups * n_specs > kcc::GRP_MAX_CELLS)
+// Argument checks of the six entry points (host or device pointers alike).
+int check_cells(kcc_ctx* ctx, const kcc::FitNodes& nd, const kcc::FitSpecs& sp, bool need_group,
+                const int64_t* totals, const int32_t* spec_err) {
+  if (nd.n < 0 || sp.S < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (nd.R < 0 || nd.R > KCC_EXT_MAX) return fail(ctx, KCC_EINVAL, "n_ext must be in [0, KCC_EXT_MAX]");
+  if (nd.G < 1) return fail(ctx, KCC_EINVAL, "n_groups must be at least 1");
+  if (!need_group && !nd.group && nd.G != 1)
+    return fail(ctx, KCC_EINVAL, "group is NULL: n_groups must be 1");
+  if (nd.n > kcc::GRP_MAX_NODES) return fail(ctx, KCC_EINVAL, "too many nodes (max 2^31 - 4096)");
+  if (sp.S > kcc::GRP_MAX_CELLS || nd.G > kcc::GRP_MAX_CELLS || nd.G * sp.S > kcc::GRP_MAX_CELLS)
     return fail(ctx, KCC_EINVAL, "too many cells: n_groups x n_specs must not exceed 2^28");
-  if (n_specs > 0 && (!spec_cpu || !spec_mem || !totals || !spec_err))
+  if (sp.S > 0 && (!sp.spec_cpu || !sp.spec_mem || !totals || !spec_err))
     return fail(ctx, KCC_EINVAL, "NULL spec array / output");
-  if (n_nodes > 0 && (!alloc_cpu || !alloc_mem || !alloc_pods || !pod_count || !used_cpu || !used_mem))
+  if (nd.n > 0 && (!nd.alloc_cpu || !nd.alloc_mem || !nd.alloc_pods || !nd.pod_count ||
+                   !nd.used_cpu || !nd.used_mem))
     return fail(ctx, KCC_EINVAL, "NULL node array");
-  if (n_nodes > 0 && !group) return fail(ctx, KCC_EINVAL, "group is NULL");
+  if (need_group && nd.n > 0 && !nd.group) return fail(ctx, KCC_EINVAL, "group is NULL");
+  if (nd.R > 0 && ((nd.n > 0 && (!nd.alloc_x || !nd.used_x)) || (sp.S > 0 && !sp.spec_x)))
+    return fail(ctx, KCC_EINVAL, "NULL extra-resource array with n_ext > 0");
   return KCC_OK;
 }
 
-int fit_grouped_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, const uint64_t* alloc_cpu,
-                    const int64_t* alloc_mem, const int64_t* alloc_pods,
-                    const int64_t* pod_count, const uint64_t* used_cpu, const int64_t* used_mem,
-                    const int32_t* group, int64_t n_groups, int64_t n_specs,
-                    const uint64_t* spec_cpu, const int64_t* spec_mem, int64_t* totals,
-                    int32_t* spec_err, hipStream_t s) {
-  int rc = check_grouped(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
-                         used_mem, group, n_groups, n_specs, spec_cpu, spec_mem, totals, spec_err);
+// Device level: the degenerate cases, the grid limit, the workspaces and the launches on s.
+// cell_min [G S] and group_rows [G] are kcc_fit_capped's outputs (nullptr elsewhere).
+int fit_cells_dev(kcc_ctx* ctx, Dev& dv, const kcc::FitNodes& nd, const kcc::FitSpecs& sp,
+                  bool need_group, int64_t* totals, int32_t* spec_err, int64_t* cell_min,
+                  int64_t* group_rows, hipStream_t s) {
+  int rc = check_cells(ctx, nd, sp, need_group, totals, spec_err);
   if (rc) return rc;
-  if (n_specs == 0) return KCC_OK;
-  const size_t cells = (size_t)(n_groups * n_specs);
-  if (n_nodes == 0) {
-    KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * cells, s));
-    KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * cells, s));
+  const size_t cells = (size_t)(nd.G * sp.S);
+  if (nd.n == 0) {  // no rows: every cell empty, every group empty
+    if (sp.S > 0) {
+      KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * cells, s));
+      KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * cells, s));
+      if (cell_min) KCC_HIP(ctx, kcc::launch_fill_i64((int64_t)cells, INT64_MAX, cell_min, s));
+    }
+    if (group_rows) KCC_HIP(ctx, hipMemsetAsync(group_rows, 0, 8 * (size_t)nd.G, s));
     return KCC_OK;
   }
-  if (kcc::grp_runs(n_nodes) * ((n_specs + kcc::GRP_PAIR_THREADS - 1) / kcc::GRP_PAIR_THREADS) >
-      0x7fffffff)
+  if (sp.S == 0 && !group_rows) return KCC_OK;  // no cells; the groups' rows are still counted
+  if (sp.S > 0 && !kcc::ext_sizes_ok(nd, sp.S))  // (check_cells has passed everything else)
     return fail(ctx, KCC_EINVAL, "n_nodes x n_specs beyond one launch (2^31 - 1 workgroups of 256 x 256 pairs)");
-  KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)n_groups));
-  KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)n_groups));
-  KCC_HIP(ctx, ensure(dv.g_total, 16));
-  KCC_HIP(ctx, ensure(dv.g_rec, sizeof(kcc::GrpRow) * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.g_rg, 4 * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.g_acc, 16 * cells));
-  const kcc::GrpWork w{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor), as<uint32_t>(dv.g_total),
-                       as<kcc::GrpRow>(dv.g_rec), as<int32_t>(dv.g_rg), as<int64_t>(dv.g_acc)};
-  KCC_HIP(ctx, kcc::launch_fit_grouped(n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count,
-                                       used_cpu, used_mem, group, n_groups, n_specs, spec_cpu,
-                                       spec_mem, w, totals, spec_err, s));
+  if (nd.group) {
+    KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)nd.G));
+    KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)nd.G));
+    KCC_HIP(ctx, ensure(dv.g_total, 16));
+  }
+  if (sp.S > 0) {
+    KCC_HIP(ctx, ensure(dv.g_rec, sizeof(kcc::GrpRow) * (size_t)nd.n));
+    KCC_HIP(ctx, ensure(dv.g_rg, 4 * (size_t)nd.n));
+    KCC_HIP(ctx, ensure(dv.g_acc, 16 * cells));
+    if (nd.R > 0) KCC_HIP(ctx, ensure(dv.x_rec, sizeof(kcc::ExtCol) * (size_t)nd.n * (size_t)nd.R));
+    if (cell_min) KCC_HIP(ctx, ensure(dv.sp_qmin, 8 * cells));
+  }
+  const kcc::ExtWork w{{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor), as<uint32_t>(dv.g_total),
+                        as<kcc::GrpRow>(dv.g_rec), as<int32_t>(dv.g_rg), as<int64_t>(dv.g_acc)},
+                       as<kcc::ExtCol>(dv.x_rec)};
+  if (sp.S == 0)
+    KCC_HIP(ctx, kcc::launch_group_rows(nd.n, nd.G, nd.group, w.g, group_rows, s));
+  else
+    KCC_HIP(ctx, kcc::launch_fit_capped(nd, sp, w, as<unsigned long long>(dv.sp_qmin), totals,
+                                        spec_err, cell_min, group_rows, s));
+  return KCC_OK;
+}
+
+int fit_cells_async(kcc_ctx* ctx, const kcc::FitNodes& nd, const kcc::FitSpecs& sp,
+                    bool need_group, int64_t* totals, int32_t* spec_err, int64_t* cell_min,
+                    int64_t* group_rows, void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  return fit_cells_dev(ctx, dv, nd, sp, need_group, totals, spec_err, cell_min, group_rows,
+                       static_cast<hipStream_t>(stream));
+}
+
+// The host array p (nullable: NULL stays NULL) copied to buf; p then names the device copy.
+template <class T>
+int stage(kcc_ctx* ctx, Dev& dv, DevBuf& buf, const T*& p, int64_t count) {
+  if (!p) return KCC_OK;
+  const int rc = h2d(ctx, dv, buf, p, count);
+  p = as<T>(buf);
+  return rc;
+}
+
+// Host level: stages the inputs, runs fit_cells_dev, copies the outputs back and syncs.
+int fit_cells_host(kcc_ctx* ctx, kcc::FitNodes nd, kcc::FitSpecs sp, bool need_group,
+                   int64_t* totals, int32_t* spec_err, int64_t* cell_min, int64_t* group_rows) {
+  if (!ctx) return KCC_EINVAL;
+  int rc = check_cells(ctx, nd, sp, need_group, totals, spec_err);
+  if (rc) return rc;
+  const int64_t n = nd.n, S = sp.S;
+  const size_t cells = (size_t)(nd.G * S);
+  if (n == 0) {
+    if (S > 0) {
+      memset(totals, 0, 8 * cells);
+      memset(spec_err, 0, 4 * cells);
+      if (cell_min)
+        for (size_t k = 0; k < cells; ++k) cell_min[k] = INT64_MAX;
+    }
+    if (group_rows) memset(group_rows, 0, 8 * (size_t)nd.G);
+    return KCC_OK;
+  }
+  if (S == 0 && !group_rows) return KCC_OK;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  if ((rc = stage(ctx, dv, dv.alloc_cpu, nd.alloc_cpu, n)) ||
+      (rc = stage(ctx, dv, dv.alloc_mem, nd.alloc_mem, n)) ||
+      (rc = stage(ctx, dv, dv.alloc_pods, nd.alloc_pods, n)) ||
+      (rc = stage(ctx, dv, dv.pod_count, nd.pod_count, n)) ||
+      (rc = stage(ctx, dv, dv.used_cpu, nd.used_cpu, n)) ||
+      (rc = stage(ctx, dv, dv.used_mem, nd.used_mem, n)) ||
+      (rc = stage(ctx, dv, dv.x_alloc, nd.alloc_x, nd.R * n)) ||
+      (rc = stage(ctx, dv, dv.x_used, nd.used_x, nd.R * n)) ||
+      (rc = stage(ctx, dv, dv.g_group, nd.group, n)) ||
+      (rc = stage(ctx, dv, dv.spec_cpu, sp.spec_cpu, S)) ||
+      (rc = stage(ctx, dv, dv.spec_mem, sp.spec_mem, S)) ||
+      (rc = stage(ctx, dv, dv.x_spec, sp.spec_x, nd.R * S)) ||
+      (rc = stage(ctx, dv, dv.sp_cap, sp.node_cap, S)))
+    return rc;
+  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
+  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
+  if (cell_min) KCC_HIP(ctx, ensure(dv.sp_cmin, 8 * cells));
+  if (group_rows) KCC_HIP(ctx, ensure(dv.sp_grows, 8 * (size_t)nd.G));
+  rc = fit_cells_dev(ctx, dv, nd, sp, need_group, as<int64_t>(dv.totals), as<int32_t>(dv.err),
+                     cell_min ? as<int64_t>(dv.sp_cmin) : nullptr,
+                     group_rows ? as<int64_t>(dv.sp_grows) : nullptr, dv.stream);
+  if (rc) return rc;
+  if (S > 0) {
+    KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
+    KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
+    if (cell_min)
+      KCC_HIP(ctx, hipMemcpyAsync(cell_min, dv.sp_cmin.p, 8 * cells, hipMemcpyDeviceToHost,
+                                  dv.stream));
+  }
+  if (group_rows)
+    KCC_HIP(ctx, hipMemcpyAsync(group_rows, dv.sp_grows.p, 8 * (size_t)nd.G,
+                                hipMemcpyDeviceToHost, dv.stream));
+  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
   return KCC_OK;
 }
 
@@ -1903,12 +1994,11 @@ int kcc_fit_grouped_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc
                           const int64_t* d_used_mem, const int32_t* d_group, int64_t n_groups,
                           int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
                           int64_t* d_totals, int32_t* d_spec_err, void* stream) {
-  if (!ctx) return KCC_EINVAL;
-  Dev& dv = ctx->devs[0];
-  KCC_HIP(ctx, hipSetDevice(dv.device));
-  return fit_grouped_dev(ctx, dv, n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count,
-                         d_used_cpu, d_used_mem, d_group, n_groups, n_specs, d_spec_cpu,
-                         d_spec_mem, d_totals, d_spec_err, static_cast<hipStream_t>(stream));
+  return fit_cells_async(ctx,
+                         {n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count, d_used_cpu,
+                          d_used_mem, 0, nullptr, nullptr, d_group, n_groups},
+                         {n_specs, d_spec_cpu, d_spec_mem, nullptr, nullptr}, true, d_totals,
+                         d_spec_err, nullptr, nullptr, stream);
 }
 
 int kcc_fit_grouped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
@@ -1916,115 +2006,12 @@ int kcc_fit_grouped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
                     const uint64_t* used_cpu, const int64_t* used_mem, const int32_t* group,
                     int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
                     const int64_t* spec_mem, int64_t* totals, int32_t* spec_err) {
-  if (!ctx) return KCC_EINVAL;
-  int rc = check_grouped(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
-                         used_mem, group, n_groups, n_specs, spec_cpu, spec_mem, totals, spec_err);
-  if (rc) return rc;
-  if (n_specs == 0) return KCC_OK;
-  const size_t cells = (size_t)(n_groups * n_specs);
-  if (n_nodes == 0) {
-    memset(totals, 0, 8 * cells);
-    memset(spec_err, 0, 4 * cells);
-    return KCC_OK;
-  }
-  Dev& dv = ctx->devs[0];
-  KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = h2d(ctx, dv, dv.alloc_cpu, alloc_cpu, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_mem, alloc_mem, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_pods, alloc_pods, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.pod_count, pod_count, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.used_cpu, used_cpu, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.used_mem, used_mem, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.g_group, group, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.spec_cpu, spec_cpu, n_specs))) return rc;
-  if ((rc = h2d(ctx, dv, dv.spec_mem, spec_mem, n_specs))) return rc;
-  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
-  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
-  rc = fit_grouped_dev(ctx, dv, n_nodes, as<uint64_t>(dv.alloc_cpu), as<int64_t>(dv.alloc_mem),
-                       as<int64_t>(dv.alloc_pods), as<int64_t>(dv.pod_count),
-                       as<uint64_t>(dv.used_cpu), as<int64_t>(dv.used_mem), as<int32_t>(dv.g_group),
-                       n_groups, n_specs, as<uint64_t>(dv.spec_cpu), as<int64_t>(dv.spec_mem),
-                       as<int64_t>(dv.totals), as<int32_t>(dv.err), dv.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  return fit_cells_host(ctx,
+                        {n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem, 0,
+                         nullptr, nullptr, group, n_groups},
+                        {n_specs, spec_cpu, spec_mem, nullptr, nullptr}, true, totals, spec_err,
+                        nullptr, nullptr);
 }
-
-}  // extern "C"
-
-
-// ---- fit with extended resources (kcc_ext.hip) ----------------------------------------
-
-namespace {
-
-// Argument checks of both ext entry points (host or device pointers alike).
-int check_ext(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
-              const int64_t* alloc_pods, const int64_t* pod_count, const uint64_t* used_cpu,
-              const int64_t* used_mem, int64_t n_ext, const int64_t* alloc_x,
-              const int64_t* used_x, const int32_t* group, int64_t n_groups, int64_t n_specs,
-              const uint64_t* spec_cpu, const int64_t* spec_mem, const int64_t* spec_x,
-              const int64_t* totals, const int32_t* spec_err) {
-  if (n_nodes < 0 || n_specs < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  if (n_ext < 0 || n_ext > KCC_EXT_MAX) return fail(ctx, KCC_EINVAL, "n_ext must be in [0, KCC_EXT_MAX]");
-  if (n_groups < 1) return fail(ctx, KCC_EINVAL, "n_groups must be at least 1");
-  if (!group && n_groups != 1) return fail(ctx, KCC_EINVAL, "group is NULL: n_groups must be 1");
-  if (n_nodes > kcc::GRP_MAX_NODES) return fail(ctx, KCC_EINVAL, "too many nodes (max 2^31 - 4096)");
-  if (n_specs > kcc::GRP_MAX_CELLS || n_groups > kcc::GRP_MAX_CELLS ||
-      n_groups * n_specs > kcc::GRP_MAX_CELLS)
-    return fail(ctx, KCC_EINVAL, "too many cells: n_groups x n_specs must not exceed 2^28");
-  if (n_specs > 0 && (!spec_cpu || !spec_mem || !totals || !spec_err))
-    return fail(ctx, KCC_EINVAL, "NULL spec array / output");
-  if (n_nodes > 0 && (!alloc_cpu || !alloc_mem || !alloc_pods || !pod_count || !used_cpu || !used_mem))
-    return fail(ctx, KCC_EINVAL, "NULL node array");
-  if (n_ext > 0 && ((n_nodes > 0 && (!alloc_x || !used_x)) || (n_specs > 0 && !spec_x)))
-    return fail(ctx, KCC_EINVAL, "NULL extra-resource array with n_ext > 0");
-  return KCC_OK;
-}
-
-int fit_ext_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, const uint64_t* alloc_cpu,
-                const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
-                const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
-                const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
-                int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
-                const int64_t* spec_mem, const int64_t* spec_x, int64_t* totals,
-                int32_t* spec_err, hipStream_t s) {
-  int rc = check_ext(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
-                     n_ext, alloc_x, used_x, group, n_groups, n_specs, spec_cpu, spec_mem, spec_x,
-                     totals, spec_err);
-  if (rc) return rc;
-  if (n_specs == 0) return KCC_OK;
-  const size_t cells = (size_t)(n_groups * n_specs);
-  if (n_nodes == 0) {
-    KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * cells, s));
-    KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * cells, s));
-    return KCC_OK;
-  }
-  if (kcc::grp_runs(n_nodes) * ((n_specs + kcc::GRP_PAIR_THREADS - 1) / kcc::GRP_PAIR_THREADS) >
-      0x7fffffff)
-    return fail(ctx, KCC_EINVAL, "n_nodes x n_specs beyond one launch (2^31 - 1 workgroups of 256 x 256 pairs)");
-  if (group) {
-    KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)n_groups));
-    KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)n_groups));
-    KCC_HIP(ctx, ensure(dv.g_total, 16));
-  }
-  KCC_HIP(ctx, ensure(dv.g_rec, sizeof(kcc::GrpRow) * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.g_rg, 4 * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.g_acc, 16 * cells));
-  KCC_HIP(ctx, ensure(dv.x_rec, sizeof(kcc::ExtCol) * (size_t)n_nodes * (size_t)n_ext));
-  const kcc::ExtWork w{{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor), as<uint32_t>(dv.g_total),
-                        as<kcc::GrpRow>(dv.g_rec), as<int32_t>(dv.g_rg), as<int64_t>(dv.g_acc)},
-                       as<kcc::ExtCol>(dv.x_rec)};
-  KCC_HIP(ctx, kcc::launch_fit_ext(n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
-                                   used_mem, (int)n_ext, alloc_x, used_x, group, n_groups, n_specs,
-                                   spec_cpu, spec_mem, spec_x, w, totals, spec_err, s));
-  return KCC_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int kcc_fit_ext_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
                       const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
@@ -2034,13 +2021,11 @@ int kcc_fit_ext_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu
                       int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
                       const int64_t* d_spec_x, int64_t* d_totals, int32_t* d_spec_err,
                       void* stream) {
-  if (!ctx) return KCC_EINVAL;
-  Dev& dv = ctx->devs[0];
-  KCC_HIP(ctx, hipSetDevice(dv.device));
-  return fit_ext_dev(ctx, dv, n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count,
-                     d_used_cpu, d_used_mem, n_ext, d_alloc_x, d_used_x, d_group, n_groups, n_specs,
-                     d_spec_cpu, d_spec_mem, d_spec_x, d_totals, d_spec_err,
-                     static_cast<hipStream_t>(stream));
+  return fit_cells_async(ctx,
+                         {n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count, d_used_cpu,
+                          d_used_mem, n_ext, d_alloc_x, d_used_x, d_group, n_groups},
+                         {n_specs, d_spec_cpu, d_spec_mem, d_spec_x, nullptr}, false, d_totals,
+                         d_spec_err, nullptr, nullptr, stream);
 }
 
 int kcc_fit_ext(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
@@ -2049,109 +2034,50 @@ int kcc_fit_ext(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const 
                 const int64_t* used_x, const int32_t* group, int64_t n_groups, int64_t n_specs,
                 const uint64_t* spec_cpu, const int64_t* spec_mem, const int64_t* spec_x,
                 int64_t* totals, int32_t* spec_err) {
-  if (!ctx) return KCC_EINVAL;
-  int rc = check_ext(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
-                     n_ext, alloc_x, used_x, group, n_groups, n_specs, spec_cpu, spec_mem, spec_x,
-                     totals, spec_err);
-  if (rc) return rc;
-  if (n_specs == 0) return KCC_OK;
-  const size_t cells = (size_t)(n_groups * n_specs);
-  if (n_nodes == 0) {
-    memset(totals, 0, 8 * cells);
-    memset(spec_err, 0, 4 * cells);
-    return KCC_OK;
-  }
-  Dev& dv = ctx->devs[0];
-  KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = h2d(ctx, dv, dv.alloc_cpu, alloc_cpu, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_mem, alloc_mem, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_pods, alloc_pods, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.pod_count, pod_count, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.used_cpu, used_cpu, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.used_mem, used_mem, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.x_alloc, alloc_x, n_ext * n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.x_used, used_x, n_ext * n_nodes))) return rc;
-  if (group && (rc = h2d(ctx, dv, dv.g_group, group, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.spec_cpu, spec_cpu, n_specs))) return rc;
-  if ((rc = h2d(ctx, dv, dv.spec_mem, spec_mem, n_specs))) return rc;
-  if ((rc = h2d(ctx, dv, dv.x_spec, spec_x, n_ext * n_specs))) return rc;
-  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
-  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
-  rc = fit_ext_dev(ctx, dv, n_nodes, as<uint64_t>(dv.alloc_cpu), as<int64_t>(dv.alloc_mem),
-                   as<int64_t>(dv.alloc_pods), as<int64_t>(dv.pod_count), as<uint64_t>(dv.used_cpu),
-                   as<int64_t>(dv.used_mem), n_ext, as<int64_t>(dv.x_alloc), as<int64_t>(dv.x_used),
-                   group ? as<int32_t>(dv.g_group) : nullptr, n_groups, n_specs,
-                   as<uint64_t>(dv.spec_cpu), as<int64_t>(dv.spec_mem), as<int64_t>(dv.x_spec),
-                   as<int64_t>(dv.totals), as<int32_t>(dv.err), dv.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  return fit_cells_host(ctx,
+                        {n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                         n_ext, alloc_x, used_x, group, n_groups},
+                        {n_specs, spec_cpu, spec_mem, spec_x, nullptr}, false, totals, spec_err,
+                        nullptr, nullptr);
 }
 
-}  // extern "C"
+int kcc_fit_capped_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                         const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
+                         const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                         const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                         const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                         int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                         const int64_t* d_spec_x, int64_t* d_totals, int32_t* d_spec_err,
+                         const int64_t* d_node_cap, int64_t* d_cell_min, int64_t* d_group_rows,
+                         void* stream) {
+  return fit_cells_async(ctx,
+                         {n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count, d_used_cpu,
+                          d_used_mem, n_ext, d_alloc_x, d_used_x, d_group, n_groups},
+                         {n_specs, d_spec_cpu, d_spec_mem, d_spec_x, d_node_cap}, false, d_totals,
+                         d_spec_err, d_cell_min, d_group_rows, stream);
+}
 
-
-// ---- spread constraints in the fit (kcc_spread.hip) -----------------------------------
-
-namespace {
-
-int fit_capped_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, const uint64_t* alloc_cpu,
+int kcc_fit_capped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
                    const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
                    const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
                    const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
                    int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
                    const int64_t* spec_mem, const int64_t* spec_x, int64_t* totals,
                    int32_t* spec_err, const int64_t* node_cap, int64_t* cell_min,
-                   int64_t* group_rows, hipStream_t s) {
-  int rc = check_ext(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
-                     n_ext, alloc_x, used_x, group, n_groups, n_specs, spec_cpu, spec_mem, spec_x,
-                     totals, spec_err);
-  if (rc) return rc;
-  const size_t cells = (size_t)(n_groups * n_specs);
-  if (n_nodes == 0) {  // no rows: every cell empty, every group empty
-    if (n_specs > 0) {
-      KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * cells, s));
-      KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * cells, s));
-      if (cell_min) KCC_HIP(ctx, kcc::launch_fill_i64((int64_t)cells, INT64_MAX, cell_min, s));
-    }
-    if (group_rows) KCC_HIP(ctx, hipMemsetAsync(group_rows, 0, 8 * (size_t)n_groups, s));
-    return KCC_OK;
-  }
-  if (n_specs == 0) {  // no cells; the groups' rows are still counted
-    if (!group_rows) return KCC_OK;
-    KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)n_groups));
-    KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)n_groups));
-    KCC_HIP(ctx, ensure(dv.g_total, 16));
-    const kcc::GrpWork g{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor),
-                         as<uint32_t>(dv.g_total), nullptr, nullptr, nullptr};
-    KCC_HIP(ctx, kcc::launch_group_rows(n_nodes, n_groups, group, g, group_rows, s));
-    return KCC_OK;
-  }
-  if (kcc::grp_runs(n_nodes) * ((n_specs + kcc::GRP_PAIR_THREADS - 1) / kcc::GRP_PAIR_THREADS) >
-      0x7fffffff)
-    return fail(ctx, KCC_EINVAL, "n_nodes x n_specs beyond one launch (2^31 - 1 workgroups of 256 x 256 pairs)");
-  if (group) {
-    KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)n_groups));
-    KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)n_groups));
-    KCC_HIP(ctx, ensure(dv.g_total, 16));
-  }
-  KCC_HIP(ctx, ensure(dv.g_rec, sizeof(kcc::GrpRow) * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.g_rg, 4 * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.g_acc, 16 * cells));
-  KCC_HIP(ctx, ensure(dv.x_rec, sizeof(kcc::ExtCol) * (size_t)n_nodes * (size_t)n_ext));
-  if (cell_min) KCC_HIP(ctx, ensure(dv.sp_qmin, 8 * cells));
-  const kcc::ExtWork w{{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor), as<uint32_t>(dv.g_total),
-                        as<kcc::GrpRow>(dv.g_rec), as<int32_t>(dv.g_rg), as<int64_t>(dv.g_acc)},
-                       as<kcc::ExtCol>(dv.x_rec)};
-  KCC_HIP(ctx, kcc::launch_fit_capped(n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count,
-                                      used_cpu, used_mem, (int)n_ext, alloc_x, used_x, group,
-                                      n_groups, n_specs, spec_cpu, spec_mem, spec_x, node_cap, w,
-                                      as<unsigned long long>(dv.sp_qmin), totals, spec_err,
-                                      cell_min, group_rows, s));
-  return KCC_OK;
+                   int64_t* group_rows) {
+  return fit_cells_host(ctx,
+                        {n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                         n_ext, alloc_x, used_x, group, n_groups},
+                        {n_specs, spec_cpu, spec_mem, spec_x, node_cap}, false, totals, spec_err,
+                        cell_min, group_rows);
 }
+
+}  // extern "C"
+
+
+// ---- spread fold: G x S cells to one total per spec (kcc_spread.hip) --------------------
+
+namespace {
 
 // Argument checks of both fold entry points.  *degenerate: nothing to launch.
 int check_fold(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs, const int64_t* cell_totals,
@@ -2205,93 +2131,6 @@ int spread_fold_dev(kcc_ctx* ctx, Dev& dv, int64_t n_groups, int64_t n_specs,
 }  // namespace
 
 extern "C" {
-
-int kcc_fit_capped_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
-                         const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
-                         const int64_t* d_pod_count, const uint64_t* d_used_cpu,
-                         const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
-                         const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
-                         int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
-                         const int64_t* d_spec_x, int64_t* d_totals, int32_t* d_spec_err,
-                         const int64_t* d_node_cap, int64_t* d_cell_min, int64_t* d_group_rows,
-                         void* stream) {
-  if (!ctx) return KCC_EINVAL;
-  Dev& dv = ctx->devs[0];
-  KCC_HIP(ctx, hipSetDevice(dv.device));
-  return fit_capped_dev(ctx, dv, n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count,
-                        d_used_cpu, d_used_mem, n_ext, d_alloc_x, d_used_x, d_group, n_groups,
-                        n_specs, d_spec_cpu, d_spec_mem, d_spec_x, d_totals, d_spec_err, d_node_cap,
-                        d_cell_min, d_group_rows, static_cast<hipStream_t>(stream));
-}
-
-int kcc_fit_capped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
-                   const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
-                   const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
-                   const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
-                   int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
-                   const int64_t* spec_mem, const int64_t* spec_x, int64_t* totals,
-                   int32_t* spec_err, const int64_t* node_cap, int64_t* cell_min,
-                   int64_t* group_rows) {
-  if (!ctx) return KCC_EINVAL;
-  int rc = check_ext(ctx, n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
-                     n_ext, alloc_x, used_x, group, n_groups, n_specs, spec_cpu, spec_mem, spec_x,
-                     totals, spec_err);
-  if (rc) return rc;
-  const size_t cells = (size_t)(n_groups * n_specs);
-  if (n_nodes == 0) {
-    if (n_specs > 0) {
-      memset(totals, 0, 8 * cells);
-      memset(spec_err, 0, 4 * cells);
-      if (cell_min)
-        for (size_t k = 0; k < cells; ++k) cell_min[k] = INT64_MAX;
-    }
-    if (group_rows) memset(group_rows, 0, 8 * (size_t)n_groups);
-    return KCC_OK;
-  }
-  if (n_specs == 0 && !group_rows) return KCC_OK;
-  Dev& dv = ctx->devs[0];
-  KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = h2d(ctx, dv, dv.alloc_cpu, alloc_cpu, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_mem, alloc_mem, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_pods, alloc_pods, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.pod_count, pod_count, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.used_cpu, used_cpu, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.used_mem, used_mem, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.x_alloc, alloc_x, n_ext * n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.x_used, used_x, n_ext * n_nodes))) return rc;
-  if (group && (rc = h2d(ctx, dv, dv.g_group, group, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.spec_cpu, spec_cpu, n_specs))) return rc;
-  if ((rc = h2d(ctx, dv, dv.spec_mem, spec_mem, n_specs))) return rc;
-  if ((rc = h2d(ctx, dv, dv.x_spec, spec_x, n_ext * n_specs))) return rc;
-  if (node_cap && (rc = h2d(ctx, dv, dv.sp_cap, node_cap, n_specs))) return rc;
-  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
-  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
-  if (cell_min) KCC_HIP(ctx, ensure(dv.sp_cmin, 8 * cells));
-  if (group_rows) KCC_HIP(ctx, ensure(dv.sp_grows, 8 * (size_t)n_groups));
-  rc = fit_capped_dev(ctx, dv, n_nodes, as<uint64_t>(dv.alloc_cpu), as<int64_t>(dv.alloc_mem),
-                      as<int64_t>(dv.alloc_pods), as<int64_t>(dv.pod_count),
-                      as<uint64_t>(dv.used_cpu), as<int64_t>(dv.used_mem), n_ext,
-                      as<int64_t>(dv.x_alloc), as<int64_t>(dv.x_used),
-                      group ? as<int32_t>(dv.g_group) : nullptr, n_groups, n_specs,
-                      as<uint64_t>(dv.spec_cpu), as<int64_t>(dv.spec_mem), as<int64_t>(dv.x_spec),
-                      as<int64_t>(dv.totals), as<int32_t>(dv.err),
-                      node_cap ? as<int64_t>(dv.sp_cap) : nullptr,
-                      cell_min ? as<int64_t>(dv.sp_cmin) : nullptr,
-                      group_rows ? as<int64_t>(dv.sp_grows) : nullptr, dv.stream);
-  if (rc) return rc;
-  if (n_specs > 0) {
-    KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
-    KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
-    if (cell_min)
-      KCC_HIP(ctx, hipMemcpyAsync(cell_min, dv.sp_cmin.p, 8 * cells, hipMemcpyDeviceToHost,
-                                  dv.stream));
-  }
-  if (group_rows)
-    KCC_HIP(ctx, hipMemcpyAsync(group_rows, dv.sp_grows.p, 8 * (size_t)n_groups,
-                                hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
-}
 
 int kcc_spread_fold_async(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs,
                           const int64_t* d_cell_totals, const int32_t* d_cell_err,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 // Diagnostic knobs produce wrong results by design (no stores, loads only), add stamp
 // stores, or make every bounded wait give up (the fault-path test build): only experiment
 // builds (csrc/Makefile `variant` / `faultdiag`, which define KCC_VARIANT_BUILD and write a
@@ -568,7 +570,12 @@ hipError_t launch_fit_rows(int64_t n, const uint64_t* alloc_cpu, const int64_t* 
                            const uint64_t* used_cpu, const int64_t* used_mem, uint64_t spec_cpu,
                            int64_t spec_mem, int64_t* q, int32_t* err, hipStream_t s);
 
-// ---- grouped fit: per node-group x spec totals (kcc_groups.hip) ------
+// ---- the cell fits: per node-group x spec totals -------------
+// kcc_fit_grouped, kcc_fit_ext and kcc_fit_capped are one path: the records (kcc_ext.hip:
+// ext_rows<R>, or kcc_groups.hip's hist / scan and ext_scatter<R> with group ids), one pair
+// loop (ext_pairs_body below, as ext_pairs<R> or kcc_spread.hip's cap_pairs<R>) and a
+// finalize.  The grouped fit is the R = 0 instance with group ids.
+//
 // The record of one node row, placed in group order: the exact path's integers (fc / fm
 // are 0 where the reference's `alloc <= used` branch divides nothing) and, for a fast row
 // (fc < 2^31, 0 <= fm < 2^50), the same two values as f64 (0.0 otherwise).
@@ -591,6 +598,7 @@ constexpr int GRP_LDS_GROUPS = 4096;   // up to this G the sort's per-workgroup 
 constexpr int64_t GRP_MAX_CELLS = (int64_t)1 << 28;  // G x S
 constexpr int64_t GRP_MAX_NODES = ((int64_t)1 << 31) - 4096;
 inline int64_t grp_runs(int64_t n_nodes) { return (n_nodes + GRP_RUN - 1) / GRP_RUN; }
+inline int64_t grp_sblocks(int64_t S) { return (S + GRP_PAIR_THREADS - 1) / GRP_PAIR_THREADS; }
 struct GrpWork {
   uint32_t* count;   // [G] rows per group
   uint32_t* cursor;  // [G] next free slot of each group (starts at the exclusive scan)
@@ -598,17 +606,13 @@ struct GrpWork {
   GrpRow* rec;       // [n] records in group order
   int32_t* rg;       // [n] the record's group | fast-row bit
   int64_t* acc;      // [2 G S] the pre-finalize pair: wrapping sums, then divide-by-zero counts
+  unsigned long long* cnt(int64_t cells) const {
+    return reinterpret_cast<unsigned long long*>(acc + cells);
+  }
 };
-// Every cell of totals / spec_err [G * S] is written.  n, G, S >= 1, G * S <= GRP_MAX_CELLS.
-hipError_t launch_fit_grouped(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
-                              const int64_t* alloc_pods, const int64_t* pod_count,
-                              const uint64_t* used_cpu, const int64_t* used_mem,
-                              const int32_t* group, int64_t G, int64_t S, const uint64_t* spec_cpu,
-                              const int64_t* spec_mem, const GrpWork& w, int64_t* totals,
-                              int32_t* spec_err, hipStream_t s);
 
-// What kcc_groups.hip and kcc_ext.hip share: the sort's constants, the launches of the
-// kernels both use (they stay in kcc_groups.hip) and the pair loop's device helpers.
+// The sort's constants, the launches of kcc_groups.hip's kernels and the pair loop's
+// device helpers.
 constexpr int GRP_SORT_THREADS = 1024;  // rows per workgroup of the hist / scatter kernels
 constexpr int GRP_ROW_FAST = 1 << 30;   // rg[]: the row's group, and this bit for a fast row
 constexpr uint64_t GRP_FC_MAX = 1ull << 31;  // fast rows: free CPU below this
@@ -655,22 +659,57 @@ struct ExtWork {
   GrpWork g;    // count / cursor / total are used only with group ids
   ExtCol* xrec;  // [n * R] record-major: the R columns of record p at xrec[p * R ...]
 };
-// group == nullptr: every row in group 0 (G must be 1), records in row order, no sort.
-// Every cell of totals / spec_err [G * S] is written.  n, G, S >= 1, 0 <= R <= EXT_MAX.
-hipError_t launch_fit_ext(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
-                          const int64_t* alloc_pods, const int64_t* pod_count,
-                          const uint64_t* used_cpu, const int64_t* used_mem, int R,
-                          const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
-                          int64_t G, int64_t S, const uint64_t* spec_cpu, const int64_t* spec_mem,
-                          const int64_t* spec_x, const ExtWork& w, int64_t* totals,
-                          int32_t* spec_err, hipStream_t s);
+// The two sides of a cell fit as the host code hands them on (kernels take scalars and
+// pointers).  The arrays are device pointers at the launchers, host or device in kcc_abi.cpp.
+struct FitNodes {
+  int64_t n;
+  const uint64_t* alloc_cpu;
+  const int64_t* alloc_mem;
+  const int64_t* alloc_pods;
+  const int64_t* pod_count;
+  const uint64_t* used_cpu;
+  const int64_t* used_mem;
+  int64_t R;               // extra resources, 0 .. EXT_MAX
+  const int64_t* alloc_x;  // [R, n] (not read with R = 0)
+  const int64_t* used_x;
+  const int32_t* group;    // nullptr: every row in group 0 (G must be 1), records in row order
+  int64_t G;
+};
+struct FitSpecs {
+  int64_t S;
+  const uint64_t* spec_cpu;
+  const int64_t* spec_mem;
+  const int64_t* spec_x;     // [R, S]
+  const int64_t* node_cap;   // [S], kcc_fit_capped alone (nullable; <= 0: no cap)
+};
+// What one call takes: n, G, S >= 1, 0 <= R <= EXT_MAX, G S <= GRP_MAX_CELLS, n <=
+// GRP_MAX_NODES and a pair-loop grid of at most 2^31 - 1 workgroups.
+inline bool ext_sizes_ok(const FitNodes& nd, int64_t S) {
+  if (nd.n <= 0 || S <= 0 || nd.G <= 0 || nd.R < 0 || nd.R > EXT_MAX || (!nd.group && nd.G != 1))
+    return false;
+  return nd.G <= GRP_MAX_CELLS && S <= GRP_MAX_CELLS && nd.G * S <= GRP_MAX_CELLS &&
+         nd.n <= GRP_MAX_NODES && grp_runs(nd.n) * grp_sblocks(S) <= 0x7fffffff;
+}
+// f(std::integral_constant<int, R>) for a runtime R: R is a template argument of the kernels.
+template <class F>
+inline hipError_t ext_dispatch(int64_t R, F&& f) {
+  static_assert(EXT_MAX == 4, "one case per R");
+  switch (R) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+  }
+  return hipErrorInvalidValue;
+}
+// Every cell of totals / spec_err [G * S] is written.  hipErrorInvalidValue unless
+// ext_sizes_ok; sp.node_cap is not read.
+hipError_t launch_fit_ext(const FitNodes& nd, const FitSpecs& sp, const ExtWork& w,
+                          int64_t* totals, int32_t* spec_err, hipStream_t s);
 // The launches of launch_fit_ext ahead of its pair loop: acc / cnt [2 G S] zeroed, then the
-// records (hist, scan and scatter with group ids; one row pass without).  Same arguments.
-hipError_t launch_ext_records(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
-                              const int64_t* alloc_pods, const int64_t* pod_count,
-                              const uint64_t* used_cpu, const int64_t* used_mem, int R,
-                              const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
-                              int64_t G, int64_t S, const ExtWork& w, hipStream_t s);
+// records (hist, scan and scatter with group ids; one row pass without).
+hipError_t launch_ext_records(const FitNodes& nd, int64_t S, const ExtWork& w, hipStream_t s);
 
 #if defined(__HIPCC__)
 constexpr unsigned long long SPREAD_SIGN = 1ull << 63;  // qmin[] cells: q ^ SPREAD_SIGN, unsigned order
@@ -796,22 +835,28 @@ __device__ inline void ext_pairs_body(
     if (qmin && live) atomicMin(qmin + (int64_t)gcur * S + s, (unsigned long long)mn ^ SPREAD_SIGN);
   }
 }
+
+// The pair loop's launch: kernel is ext_pairs_kernel<R>, or cap_pairs_kernel<R> with its two
+// last arguments (node_cap, qmin) in tail.  The caller has passed ext_sizes_ok.
+template <class Kernel, class... Tail>
+inline hipError_t launch_pairs(Kernel kernel, const FitNodes& nd, const FitSpecs& sp,
+                               const ExtWork& w, hipStream_t s, Tail... tail) {
+  const int64_t sblocks = grp_sblocks(sp.S);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(grp_runs(nd.n) * sblocks)), dim3(GRP_PAIR_THREADS), 0,
+                     s, nd.group ? w.g.total : (const uint32_t*)nullptr, nd.n, sp.S, sblocks,
+                     sp.spec_cpu, sp.spec_mem, sp.spec_x, w.g.rec, w.xrec, w.g.rg, w.g.acc,
+                     w.g.cnt(nd.G * sp.S), tail...);
+  return hipGetLastError();
+}
 #endif
 
 // ---- spread constraints in the fit (kcc_spread.hip) ----------------
-// kcc_fit_capped: launch_fit_ext's arguments, then node_cap [S] (nullable; <= 0: no cap),
-// qmin [G S] (workspace of cell_min; unused when cell_min is nullptr), and the nullable
-// outputs cell_min [G S] and group_rows [G].  node_cap and cell_min both nullptr: the
-// launches of launch_fit_ext themselves.
-hipError_t launch_fit_capped(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
-                             const int64_t* alloc_pods, const int64_t* pod_count,
-                             const uint64_t* used_cpu, const int64_t* used_mem, int R,
-                             const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
-                             int64_t G, int64_t S, const uint64_t* spec_cpu,
-                             const int64_t* spec_mem, const int64_t* spec_x,
-                             const int64_t* node_cap, const ExtWork& w, unsigned long long* qmin,
-                             int64_t* totals, int32_t* spec_err, int64_t* cell_min,
-                             int64_t* group_rows, hipStream_t s);
+// kcc_fit_capped: launch_fit_ext with sp.node_cap, qmin [G S] (workspace of cell_min; unused
+// when cell_min is nullptr), and the nullable outputs cell_min [G S] and group_rows [G].
+// node_cap and cell_min both nullptr: the launches of launch_fit_ext themselves.
+hipError_t launch_fit_capped(const FitNodes& nd, const FitSpecs& sp, const ExtWork& w,
+                             unsigned long long* qmin, int64_t* totals, int32_t* spec_err,
+                             int64_t* cell_min, int64_t* group_rows, hipStream_t s);
 // group_rows alone (no specs): grp_hist's counts widened; group == nullptr: out[0] = n.
 hipError_t launch_group_rows(int64_t n, int64_t G, const int32_t* group, const GrpWork& w,
                              int64_t* group_rows, hipStream_t s);

@@ -8,7 +8,8 @@
 //                     group ids; ext_rows<R> without
 //   cap_pairs<R>      ext_pairs<R>'s body (ext_pairs_body in kcc_internal.h) with SPREAD set:
 //                     two 64-bit compare-and-selects per pair after the one conversion, and a
-//                     64-bit atomic min beside grp_flush's atomic add
+//                     64-bit atomic min beside grp_flush's atomic add; launched as ext_pairs<R>
+//                     is (launch_pairs, R through ext_dispatch, both in kcc_internal.h)
 //   cap_finalize      grp_finalize plus cell_min (the cells hold q with the sign bit flipped,
 //                     so a byte fill of 0xFF is the identity of the unsigned atomic min)
 //   grp_rows          group_rows = grp_hist's counts widened to int64
@@ -143,18 +144,6 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_finish_kernel(
   spec_err[s] = 0;
 }
 
-template <int R>
-void launch_cap_pairs(int64_t n, const int32_t* group, int64_t S, const uint64_t* spec_cpu,
-                      const int64_t* spec_mem, const int64_t* spec_x, const int64_t* node_cap,
-                      const ExtWork& w, int64_t* acc, unsigned long long* cnt,
-                      unsigned long long* qmin, hipStream_t s) {
-  const int64_t sblocks = (S + GRP_PAIR_THREADS - 1) / GRP_PAIR_THREADS;
-  const int64_t pair_grid = grp_runs(n) * sblocks;
-  hipLaunchKernelGGL(cap_pairs_kernel<R>, dim3((unsigned)pair_grid), dim3(GRP_PAIR_THREADS), 0, s,
-                     group ? w.g.total : (const uint32_t*)nullptr, n, S, sblocks, spec_cpu,
-                     spec_mem, spec_x, w.g.rec, w.xrec, w.g.rg, acc, cnt, node_cap, qmin);
-}
-
 }  // namespace
 
 hipError_t launch_fill_i64(int64_t cells, int64_t v, int64_t* out, hipStream_t s) {
@@ -174,46 +163,29 @@ hipError_t launch_group_rows(int64_t n, int64_t G, const int32_t* group, const G
   return hipGetLastError();
 }
 
-hipError_t launch_fit_capped(int64_t n, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
-                             const int64_t* alloc_pods, const int64_t* pod_count,
-                             const uint64_t* used_cpu, const int64_t* used_mem, int R,
-                             const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
-                             int64_t G, int64_t S, const uint64_t* spec_cpu,
-                             const int64_t* spec_mem, const int64_t* spec_x,
-                             const int64_t* node_cap, const ExtWork& w, unsigned long long* qmin,
-                             int64_t* totals, int32_t* spec_err, int64_t* cell_min,
-                             int64_t* group_rows, hipStream_t s) {
+hipError_t launch_fit_capped(const FitNodes& nd, const FitSpecs& sp, const ExtWork& w,
+                             unsigned long long* qmin, int64_t* totals, int32_t* spec_err,
+                             int64_t* cell_min, int64_t* group_rows, hipStream_t s) {
   hipError_t e;
-  if (!node_cap && !cell_min) {
+  if (!sp.node_cap && !cell_min) {
     // kcc_fit_ext's own launches (with group ids they leave grp_hist's counts in w.g.count)
-    e = launch_fit_ext(n, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem, R,
-                       alloc_x, used_x, group, G, S, spec_cpu, spec_mem, spec_x, w, totals,
-                       spec_err, s);
-    if (e != hipSuccess) return e;
+    if ((e = launch_fit_ext(nd, sp, w, totals, spec_err, s)) != hipSuccess) return e;
   } else {
     if (cell_min && !qmin) return hipErrorInvalidValue;
-    e = launch_ext_records(n, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem, R,
-                           alloc_x, used_x, group, G, S, w, s);
-    if (e != hipSuccess) return e;
-    const int64_t cells = G * S;
-    int64_t* acc = w.g.acc;
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(w.g.acc + cells);
+    if ((e = launch_ext_records(nd, sp.S, w, s)) != hipSuccess) return e;
+    const int64_t cells = nd.G * sp.S;
     unsigned long long* qm = cell_min ? qmin : nullptr;
     if (qm && (e = hipMemsetAsync(qm, 0xFF, 8 * (size_t)cells, s)) != hipSuccess) return e;
-    switch (R) {
-      case 0: launch_cap_pairs<0>(n, group, S, spec_cpu, spec_mem, spec_x, node_cap, w, acc, cnt, qm, s); break;
-      case 1: launch_cap_pairs<1>(n, group, S, spec_cpu, spec_mem, spec_x, node_cap, w, acc, cnt, qm, s); break;
-      case 2: launch_cap_pairs<2>(n, group, S, spec_cpu, spec_mem, spec_x, node_cap, w, acc, cnt, qm, s); break;
-      case 3: launch_cap_pairs<3>(n, group, S, spec_cpu, spec_mem, spec_x, node_cap, w, acc, cnt, qm, s); break;
-      case 4: launch_cap_pairs<4>(n, group, S, spec_cpu, spec_mem, spec_x, node_cap, w, acc, cnt, qm, s); break;
-      default: return hipErrorInvalidValue;
-    }
+    e = ext_dispatch(nd.R, [&](auto r) {
+      return launch_pairs(cap_pairs_kernel<decltype(r)::value>, nd, sp, w, s, sp.node_cap, qm);
+    });
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(cap_finalize_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s,
-                       cells, acc, cnt, qm, totals, spec_err, cell_min);
+                       cells, w.g.acc, w.g.cnt(cells), qm, totals, spec_err, cell_min);
   }
   if (group_rows)
-    hipLaunchKernelGGL(grp_rows_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, G,
-                       group ? w.g.count : (const uint32_t*)nullptr, n, group_rows);
+    hipLaunchKernelGGL(grp_rows_kernel, dim3((unsigned)((nd.G + 255) / 256)), dim3(256), 0, s, nd.G,
+                       nd.group ? w.g.count : (const uint32_t*)nullptr, nd.n, group_rows);
   return hipGetLastError();
 }
 

@@ -140,26 +140,46 @@ class CapacityEngine:
                                       _p(totals), _p(err)))
         return totals, err
 
+    def _cell_args(self, rows6, spec_cpu, spec_mem, group, n_groups, alloc_x=None, used_x=None,
+                   spec_x=None):
+        """What fit_grouped, fit_ext and fit_capped share: coercion, the shape checks and the
+        [G, S] outputs.  Returns (a, R, ax, ux, group, G, sc, sm, sx, totals, err): a the six
+        node columns; alloc_x / used_x / spec_x None: no extra resource (R = 0)."""
+        a = [_arr(x, t) for x, t in zip(rows6, (np.uint64, np.int64, np.int64, np.int64,
+                                                np.uint64, np.int64))]
+        n = a[0].size
+        if group is not None:
+            group = _key32(group)
+        if any(x.size != n for x in a) or (group is not None and group.size != n):
+            raise ValueError("node arrays differ in length")
+        sc, sm = _arr(spec_cpu, np.uint64), _arr(spec_mem, np.int64)
+        if sc.size != sm.size:
+            raise ValueError("spec arrays differ in length")
+        S = sc.size
+        ax = _arr(np.zeros((0, n)) if alloc_x is None else alloc_x, np.int64)
+        ux = _arr(np.zeros((0, n)) if used_x is None else used_x, np.int64)
+        sx = _arr(np.zeros((0, S)) if spec_x is None else spec_x, np.int64)
+        if ax.ndim != 2 or ux.shape != ax.shape or ax.shape[1] != n:
+            raise ValueError("alloc_x and used_x must both be [R, N]")
+        R = ax.shape[0]
+        if sx.shape != (R, S):
+            raise ValueError("spec_x must be [R, S]")
+        G = int(n_groups)
+        totals = np.zeros((max(G, 0), S), np.int64)
+        err = np.zeros((max(G, 0), S), np.int32)
+        return a, R, ax, ux, group, G, sc, sm, sx, totals, err
+
     def fit_grouped(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
                     group, n_groups, spec_cpu, spec_mem):
         """CC:101-140 per node group: totals[g, s] is total_possible_max_replicas on the rows
         with group[i] == g (ids < 0 or >= n_groups: skipped), err[g, s] = 1 where Go would
         panic on that sub-cluster.  Returns (totals int64[G, S], err int32[G, S]); a
         selector's answer is select_groups over its eligible groups."""
-        a = [_arr(alloc_cpu, np.uint64), _arr(alloc_mem, np.int64), _arr(alloc_pods, np.int64),
-             _arr(pod_count, np.int64), _arr(used_cpu, np.uint64), _arr(used_mem, np.int64)]
-        n = a[0].size
-        group = _key32(group)
-        if any(x.size != n for x in a) or group.size != n:
-            raise ValueError("node arrays differ in length")
-        sc, sm = _arr(spec_cpu, np.uint64), _arr(spec_mem, np.int64)
-        if sc.size != sm.size:
-            raise ValueError("spec arrays differ in length")
-        G = int(n_groups)
-        totals = np.zeros((max(G, 0), sc.size), np.int64)
-        err = np.zeros((max(G, 0), sc.size), np.int32)
-        self._check(self._lib.kcc_fit_grouped(self._h, n, *[_p(x) for x in a], _p(group), G,
-                                              sc.size, _p(sc), _p(sm), _p(totals), _p(err)))
+        a, _, _, _, group, G, sc, sm, _, totals, err = self._cell_args(
+            (alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem), spec_cpu, spec_mem,
+            group, n_groups)
+        self._check(self._lib.kcc_fit_grouped(self._h, a[0].size, *[_p(x) for x in a], _p(group),
+                                              G, sc.size, _p(sc), _p(sm), _p(totals), _p(err)))
         return totals, err
 
     def fit_grouped_async(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
@@ -183,29 +203,11 @@ class CapacityEngine:
         follows all the mins.  R = 0 is total_possible_max_replicas (group None) or
         fit_grouped.  Returns (totals int64, err int32) of shape [S] without group ids and
         [n_groups, S] with them."""
-        a = [_arr(alloc_cpu, np.uint64), _arr(alloc_mem, np.int64), _arr(alloc_pods, np.int64),
-             _arr(pod_count, np.int64), _arr(used_cpu, np.uint64), _arr(used_mem, np.int64)]
-        n = a[0].size
-        if any(x.size != n for x in a):
-            raise ValueError("node arrays differ in length")
-        sc, sm = _arr(spec_cpu, np.uint64), _arr(spec_mem, np.int64)
-        if sc.size != sm.size:
-            raise ValueError("spec arrays differ in length")
-        ax, ux, sx = _arr(alloc_x, np.int64), _arr(used_x, np.int64), _arr(spec_x, np.int64)
-        if ax.ndim != 2 or ux.shape != ax.shape or ax.shape[1] != n:
-            raise ValueError("alloc_x and used_x must both be [R, N]")
-        R = ax.shape[0]
-        if sx.shape != (R, sc.size):
-            raise ValueError("spec_x must be [R, S]")
-        G = int(n_groups)
-        if group is not None:
-            group = _key32(group)
-            if group.size != n:
-                raise ValueError("node arrays differ in length")
-        totals = np.zeros((max(G, 0), sc.size), np.int64)
-        err = np.zeros((max(G, 0), sc.size), np.int32)
-        self._check(self._lib.kcc_fit_ext(self._h, n, *[_p(x) for x in a], R, _p(ax), _p(ux),
-                                          _p(group), G, sc.size, _p(sc), _p(sm), _p(sx),
+        a, R, ax, ux, group, G, sc, sm, sx, totals, err = self._cell_args(
+            (alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem), spec_cpu, spec_mem,
+            group, n_groups, alloc_x, used_x, spec_x)
+        self._check(self._lib.kcc_fit_ext(self._h, a[0].size, *[_p(x) for x in a], R, _p(ax),
+                                          _p(ux), _p(group), G, sc.size, _p(sc), _p(sm), _p(sx),
                                           _p(totals), _p(err)))
         if group is None:
             return totals[0], err[0]
@@ -239,37 +241,17 @@ class CapacityEngine:
         None, group_rows int64 [n_groups] or None); the first three are [S] without group ids
         and [n_groups, S] with them.  A flagged cell has cell_min 0, a cell with no rows
         INT64_MAX."""
-        a = [_arr(alloc_cpu, np.uint64), _arr(alloc_mem, np.int64), _arr(alloc_pods, np.int64),
-             _arr(pod_count, np.int64), _arr(used_cpu, np.uint64), _arr(used_mem, np.int64)]
-        n = a[0].size
-        if any(x.size != n for x in a):
-            raise ValueError("node arrays differ in length")
-        sc, sm = _arr(spec_cpu, np.uint64), _arr(spec_mem, np.int64)
-        if sc.size != sm.size:
-            raise ValueError("spec arrays differ in length")
+        a, R, ax, ux, group, G, sc, sm, sx, totals, err = self._cell_args(
+            (alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem), spec_cpu, spec_mem,
+            group, n_groups, alloc_x, used_x, spec_x)
         S = sc.size
-        ax = _arr(np.zeros((0, n)) if alloc_x is None else alloc_x, np.int64)
-        ux = _arr(np.zeros((0, n)) if used_x is None else used_x, np.int64)
-        sx = _arr(np.zeros((0, S)) if spec_x is None else spec_x, np.int64)
-        if ax.ndim != 2 or ux.shape != ax.shape or ax.shape[1] != n:
-            raise ValueError("alloc_x and used_x must both be [R, N]")
-        R = ax.shape[0]
-        if sx.shape != (R, S):
-            raise ValueError("spec_x must be [R, S]")
-        G = int(n_groups)
-        if group is not None:
-            group = _key32(group)
-            if group.size != n:
-                raise ValueError("node arrays differ in length")
         cap = None if node_cap is None else _arr(node_cap, np.int64)
         if cap is not None and cap.shape != (S,):
             raise ValueError("node_cap must be [S]")
-        totals = np.zeros((max(G, 0), S), np.int64)
-        err = np.zeros((max(G, 0), S), np.int32)
         cmin = np.zeros((max(G, 0), S), np.int64) if want_min else None
         grows = np.zeros(max(G, 0), np.int64) if want_rows else None
-        self._check(self._lib.kcc_fit_capped(self._h, n, *[_p(x) for x in a], R, _p(ax), _p(ux),
-                                             _p(group), G, S, _p(sc), _p(sm), _p(sx),
+        self._check(self._lib.kcc_fit_capped(self._h, a[0].size, *[_p(x) for x in a], R, _p(ax),
+                                             _p(ux), _p(group), G, S, _p(sc), _p(sm), _p(sx),
                                              _p(totals), _p(err), _p(cap), _p(cmin), _p(grows)))
         if group is None:
             return totals[0], err[0], None if cmin is None else cmin[0], grows

@@ -240,3 +240,11 @@ def test_kernels_compile_without_scratch(tmp_path):
             assert hit[0]["group_segment_fixed_size"] <= LDS_STATIC_MAX, (k, r)
     assert len(meta) == len(KERNELS) * (_lib.KCC_EXT_MAX + 1)
     assert set(re.findall(r"; ScratchSize: (\d+)", asm)) == {"0"}
+    # the R = 0 instances are the grouped fit's kernels: the pair loop's 8
+    # waves per SIMD (<= 64 VGPRs) and 256 x (48 + 4) B of staged records, the scatter's
+    # GRP_LDS_GROUPS x 4 B of per-workgroup counts
+    pairs0, = [v for name, v in meta.items() if "ext_pairs_kernelILi0E" in name]
+    scatter0, = [v for name, v in meta.items() if "ext_scatter_kernelILi0E" in name]
+    assert pairs0["group_segment_fixed_size"] == 13312 and pairs0["vgpr_count"] <= 64, pairs0
+    assert scatter0["group_segment_fixed_size"] == 16384, scatter0
+    assert pairs0["private_segment_fixed_size"] == 0 == scatter0["private_segment_fixed_size"]

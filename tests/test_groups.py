@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from kubernetesclustercapacity_amd import _lib, synth
+from kubernetesclustercapacity_amd import KccError, _lib, synth
 from oracle import coracle
 
 U64 = 1 << 64
@@ -296,9 +296,65 @@ def test_gpu_grouped_argument_errors(eng):
                                       p(t), p(e))
         return rc, eng._lib.kcc_last_error(eng._h).decode()
 
+    # (None, 1, 2): kcc_fit_ext takes a NULL group with one group; the grouped call does not
     for group, G, S in [(gid, 0, 2), (gid, -1, 2), (gid, (1 << 27) + 1, 2), (gid, 1 << 28, 2),
-                        (gid, 1 << 62, 1 << 62), (None, 4, 2)]:
+                        (gid, 1 << 62, 1 << 62), (None, 4, 2), (None, 1, 2)]:
         rc, msg = call(group, G, S)
         assert rc == _lib.KCC_EINVAL and msg, (G, S)
     rc, msg = call(gid, 4, 2)  # the same buffers with valid sizes
     assert rc == 0, msg
+    # the device form with a NULL group pointer
+    import torch
+    dev = torch.device("cuda", 0)
+    d = [torch.zeros(4, dtype=torch.int64, device=dev) for _ in range(6)]
+    dsc, dsm = [torch.ones(2, dtype=torch.int64, device=dev) for _ in range(2)]
+    dt = torch.zeros(8, dtype=torch.int64, device=dev)
+    de = torch.zeros(8, dtype=torch.int32, device=dev)
+    for G in (1, 4):
+        with pytest.raises(KccError) as ei:
+            eng.fit_grouped_async(*d, None, G, dsc, dsm, dt, de)
+        assert ei.value.code == _lib.KCC_EINVAL
+        assert eng._lib.kcc_last_error(eng._h).decode()
+    torch.cuda.synchronize()
+
+
+def _raw_cells(eng, entry, rows, gid, G, sc, sm):
+    """kcc_fit_ext (n_ext = 0) or kcc_fit_capped (every optional pointer NULL) through the
+    C-ABI itself; the outputs start at 77 so a cell left unwritten shows."""
+    p = lambda x: None if x is None else C.c_void_p(x.ctypes.data)  # noqa: E731
+    rows = [np.ascontiguousarray(a, d) for a, d in zip(rows, (np.uint64, np.int64, np.int64,
+                                                              np.int64, np.uint64, np.int64))]
+    sc, sm = np.ascontiguousarray(sc, np.uint64), np.ascontiguousarray(sm, np.int64)
+    n, S = rows[0].size, sc.size
+    t = np.full((G, S), 77, np.int64)
+    e = np.full((G, S), 77, np.int32)
+    args = [eng._h, n, *[p(a) for a in rows], 0, None, None, p(gid), G, S, p(sc), p(sm), None,
+            p(t), p(e)]
+    if entry == "kcc_fit_capped":
+        args += [None, None, None]
+    rc = getattr(eng._lib, entry)(*args)
+    assert rc == 0, eng._lib.kcc_last_error(eng._h).decode()
+    return t, e
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G", [1, 3, 4097])
+def test_gpu_three_entry_points_are_one_path(eng, G):
+    """kcc_fit_grouped, kcc_fit_ext with n_ext = 0 and kcc_fit_capped with no cap, no cell_min
+    and no group_rows give the same bits in every cell, and they are the oracle's.  n = 1025:
+    two scatter workgroups of 1024 rows and five pair-loop runs of 256, the last of one row;
+    S = 65: a second wave with one live lane; G = 4097 > GRP_LDS_GROUPS sorts with global
+    atomics; 3 % of the ids lie outside [0, G)."""
+    n, S = 1025, 65
+    rows = cached_rows(n)
+    sc, sm = synth.make_specs(S, seed=3, adversarial=True)
+    gid = group_ids(n, G, 3)
+    assert ((gid < 0) | (gid >= G)).any()
+    t, e = eng.fit_grouped(*rows, gid, G, sc, sm)
+    ot, oe = expected(rows, gid, G, sc, sm)
+    assert t.shape == e.shape == ot.shape == (G, S)
+    assert np.array_equal(e, oe) and np.array_equal(t, ot)
+    for entry in ("kcc_fit_ext", "kcc_fit_capped"):
+        xt, xe = _raw_cells(eng, entry, rows, gid, G, sc, sm)
+        assert np.array_equal(xe, e) and np.array_equal(xt, t), entry
+    assert (e != 0).any() and (e == 0).any()

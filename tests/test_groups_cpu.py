@@ -3,7 +3,7 @@
   - the header declares both entry points and _lib.SIGNATURES binds them with its arity;
   - select_groups (host arithmetic on the G x S cells) against the C oracle run on the
     union of the eligible groups' rows;
-  - a model of the pair loop's fast path (kcc_groups.hip grp_div), restated in numpy f64
+  - a model of the pair loop's fast path (kcc_internal.h grp_div), restated in numpy f64
     and Python integers, against exact division on the stated bounds
         fast row : free CPU < 2^31, 0 <= free memory < 2^50
         fast spec: 1 <= c <= 2^52, 1 <= m <= 2^52
@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "kubernetesclustercapacity_amd", "csrc", "kcc_groups.hip")
 U64 = 1 << 64
 
-FC_MAX = 1 << 31    # kcc_groups.hip GRP_FC_MAX
+FC_MAX = 1 << 31    # kcc_internal.h GRP_FC_MAX
 FM_MAX = 1 << 50    # GRP_FM_MAX
 SPEC_MAX = 1 << 52  # GRP_SPEC_MAX
 
@@ -211,8 +211,9 @@ def test_fast_pair_clamp_model():
 HIPCC = shutil.which("hipcc") or shutil.which(
     os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc"))
 
-KERNELS = ["grp_hist_kernel", "grp_scan_kernel", "grp_scatter_kernel", "grp_pairs_kernel",
-           "grp_finalize_kernel"]
+# what every cell fit shares; the scatter and the pair loop are kcc_ext.hip's R = 0 instances
+# (tests/test_ext_cpu.py checks their registers and LDS)
+KERNELS = ["grp_hist_kernel", "grp_scan_kernel", "grp_finalize_kernel"]
 
 
 @pytest.mark.skipif(HIPCC is None, reason="hipcc not available")
