@@ -12,6 +12,9 @@
     with NEW inputs each time == the oracle for each input (no launch depends on host
     state a replay would freeze: the look-back records are left free by every launch,
     the exchange epoch is a device word).  ClusterCapacity.go:101-140, 290-293.
+  - hipGraph capture of the cell fits: kcc_fit_capped_async + kcc_spread_fold_async in one
+    graph, kcc_fit_grouped_async and kcc_fit_ext_async, replayed over inputs whose group ids
+    give another *total and other cursors each time == the Python-integer models.
 """
 import os
 
@@ -294,3 +297,151 @@ def test_graph_replay_capacity_async(mode):
                 np.testing.assert_array_equal(err.cpu().numpy(), e, err_msg=msg)
         assert eng.reduce_faults() == 0
         del g
+
+
+# ---- the cell fits and the fold in a graph (include/kcc.h: "allocate only when a size exceeds
+# every earlier call's and never synchronise"; "no readback between the pair pass and the
+# fold: both can be captured into one graph") -------------------------------------------------
+CELL_N, CELL_S, CELL_R = 1025, 65, 2
+CELL_VARIANTS = [(71, "uniform"), (72, "one"), (73, "invalid40")]  # (seed, id layout)
+_CELL = {}
+
+
+def _cell_variant(k, R):
+    """Variant k's inputs and the model's pair table (computed once, never modified)."""
+    from tests import test_gpu_fuzz_cells as fz
+    if (k, R) not in _CELL:
+        case = fz.make_cell_case(CELL_VARIANTS[k][0], CELL_N, CELL_S, R)
+        _CELL[k, R] = (case, fz.pair_model(case))
+    return _CELL[k, R]
+
+
+def _replay_cells(capture, bufs, new, outs, check):
+    """test_graph_replay_capacity_async's pattern: a fresh engine, one warm-up call of the
+    captured entries on the stream, the capture (a linear chain), then each variant's inputs
+    copied into the captured buffers, every output filled with a sentinel, a replay and
+    check(k, msg) after a stream synchronise; three variants, twice each in rotation."""
+    import torch
+
+    from kubernetesclustercapacity_amd import CapacityEngine
+    dev = torch.device("cuda", 0)
+    with CapacityEngine(0, 1) as eng:
+        stream = torch.cuda.Stream(dev)
+        with torch.cuda.stream(stream):  # warm-up: every workspace allocated
+            capture(eng, stream)
+        stream.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=stream):
+            capture(eng, stream)
+        for rep in range(2):
+            for k in range(len(new)):
+                with torch.cuda.stream(stream):
+                    for key, t in bufs.items():
+                        t.copy_(new[k][key])
+                    for t in outs.values():
+                        t.fill_(77)
+                    g.replay()
+                stream.synchronize()
+                check(k, f"replay {rep} variant {k}")
+        assert eng.reduce_faults() == 0
+        del g
+
+
+def _to_dev(a, dev):
+    import torch
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
+
+
+@pytest.mark.parametrize("which", ["capped+fold", "grouped", "ext ungrouped"])
+def test_graph_replay_cell_fits(which):
+    """kcc_fit_capped_async + kcc_spread_fold_async in one graph (G = 7, no readback between
+    them), kcc_fit_grouped_async (G = 4097: the global-atomic sort) and kcc_fit_ext_async
+    without group ids (ext_rows, no *total), each captured once and replayed over three
+    variants that differ in values and in id layout — so in *total (about 994, 1025 and 615
+    valid rows: whole runs past *total in two of the three), in every cursor and in every run's
+    group changes: every output == the models each time, and with no extra resource == the C
+    oracle on each group's rows."""
+    import torch
+
+    from conftest import init_torch_first
+    from tests import ext_model as xm
+    from tests import spread_model as spm
+    from tests import test_gpu_fuzz_cells as fz
+    from tests.test_groups import expected
+    init_torch_first()
+    dev = torch.device("cuda", 0)
+    n, S = CELL_N, CELL_S
+    R = 0 if which == "grouped" else CELL_R
+    G = {"capped+fold": 7, "grouped": 4097, "ext ungrouped": 1}[which]
+    D = 3
+    variants, new = [], []
+    for k, (seed, kind) in enumerate(CELL_VARIANTS):
+        case, (q, dz) = _cell_variant(k, R)
+        gid = None if which == "ext ungrouped" else fz.group_layout(seed, n, G, kind)
+        rng = np.random.default_rng([seed, 0x6A])
+        v = dict(case=case, q=q, dz=dz, gid=gid, cap=fz.node_caps(seed, S),
+                 dom=np.array([0, 1, 2, 0, 1, 5, 2], np.int32)[rng.permutation(7)],
+                 el=(rng.random((7, S)) < 0.7).astype(np.uint8),
+                 sk=rng.choice(np.array(fz.SKEWS, np.int64), S))
+        variants.append(v)
+        d = {f"row{i}": _to_dev(a, dev) for i, a in enumerate(case["rows"])}
+        d.update(sc=_to_dev(case["sc"], dev), sm=_to_dev(case["sm"], dev))
+        if R:
+            d.update(ax=_to_dev(case["ax"], dev), ux=_to_dev(case["ux"], dev),
+                     sx=_to_dev(case["sx"], dev))
+        if gid is not None:
+            d["gid"] = _to_dev(gid, dev)
+        if which == "capped+fold":
+            d.update(cap=_to_dev(v["cap"], dev), dom=_to_dev(v["dom"], dev),
+                     el=_to_dev(v["el"], dev), sk=_to_dev(v["sk"], dev))
+        new.append(d)
+    valid = [n if v["gid"] is None else int(((v["gid"] >= 0) & (v["gid"] < G)).sum())
+             for v in variants]
+    if which != "ext ungrouped":  # *total differs per replay; two variants leave runs unused
+        assert len(set(valid)) == 3 and valid[1] == n and valid[2] < n - 256, valid
+    bufs = {key: t.clone() for key, t in new[0].items()}
+    rows = [bufs[f"row{i}"] for i in range(6)]
+    full = lambda k, t: torch.empty(k, dtype=t, device=dev)  # noqa: E731
+    outs = dict(t=full(G * S, torch.int64), e=full(G * S, torch.int32))
+    if which == "capped+fold":
+        outs.update(m=full(G * S, torch.int64), r=full(G, torch.int64), ft=full(S, torch.int64),
+                    fe=full(S, torch.int32))
+
+    def capture(eng, stream):
+        if which == "capped+fold":
+            eng.fit_capped_async(*rows, R, bufs["ax"], bufs["ux"], bufs["gid"], G, bufs["sc"],
+                                 bufs["sm"], bufs["sx"], outs["t"], outs["e"], bufs["cap"],
+                                 outs["m"], outs["r"], stream=stream)
+            eng.spread_fold_async(G, S, outs["t"], outs["e"], outs["r"], bufs["dom"], D,
+                                  bufs["el"], bufs["sk"], outs["ft"], outs["fe"], stream=stream)
+        elif which == "grouped":
+            eng.fit_grouped_async(*rows, bufs["gid"], G, bufs["sc"], bufs["sm"], outs["t"],
+                                  outs["e"], stream=stream)
+        else:
+            eng.fit_ext_async(*rows, R, bufs["ax"], bufs["ux"], None, 1, bufs["sc"], bufs["sm"],
+                              bufs["sx"], outs["t"], outs["e"], stream=stream)
+
+    def want(k):
+        """The models' outputs of variant k, by output name (computed once)."""
+        v = variants[k]
+        if "want" not in v:
+            if which == "capped+fold":
+                t, e, m, r = spm.capped_cells(v["q"], v["dz"], v["gid"], G, v["cap"])
+                ft, fe, _ = spm.fold(t, e, r, v["dom"], D, v["el"], v["sk"])
+                v["want"] = dict(t=t, e=e, m=m, r=r, ft=ft, fe=fe)
+            else:
+                t, e = xm.totals_from_pairs(v["q"], v["dz"], v["gid"], G)
+                v["want"] = dict(t=t, e=e)
+                if which == "grouped":  # R = 0: the C oracle on each group's rows agrees
+                    ot, oe = expected(v["case"]["rows"], v["gid"], G, v["case"]["sc"],
+                                      v["case"]["sm"])
+                    assert np.array_equal(ot, t) and np.array_equal(oe, e)
+        return v["want"]
+
+    def check(k, msg):
+        for key, w in want(k).items():
+            got = outs[key].cpu().numpy().reshape(w.shape)
+            np.testing.assert_array_equal(got, w, err_msg=f"{which} {key}: {msg}")
+
+    _replay_cells(capture, bufs, new, outs, check)

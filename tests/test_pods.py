@@ -17,16 +17,28 @@ U64 = 1 << 64
 I64_MIN = -(1 << 63)
 
 
-def pods_case(seed, n_nodes=300, mean_pods=6, extremes=False):
+LONG_APP = [0, 1, 3, 4, 5, 7, 8, 9, 17, 64]  # around kcc_pods.hip POD_BATCH = 4 round trips
+LONG_INIT = [0, 1, 2, 3, 4, 5, 9]            # around INIT_BATCH = 2 round trips
+
+
+def pods_case(seed, n_nodes=300, mean_pods=6, extremes=False, long_pods=False, n_pods=None):
     """Seeded pods grouped by node: 1-3 app containers, 0-3 init containers (some
-    restartable), overhead on some pods."""
+    restartable), overhead on some pods.  long_pods: the app container count from LONG_APP
+    and the init container count from LONG_INIT, and on a third of the pods the restartable
+    entries in runs (sidecars before and after the regular init containers).  n_pods: exactly
+    that many pods, all on one node (no Poisson draw)."""
     rng = np.random.default_rng(seed)
-    ppn = rng.poisson(mean_pods, n_nodes)
+    ppn = rng.poisson(mean_pods, n_nodes) if n_pods is None else np.array([n_pods])
+    n_nodes = ppn.size
     node_pod_ptr = np.zeros(n_nodes + 1, np.int64)
     node_pod_ptr[1:] = np.cumsum(ppn)
     P = int(node_pod_ptr[-1])
-    nc = rng.integers(1, 4, P)
-    ni = rng.choice([0, 0, 1, 2, 3], P)
+    if long_pods:
+        nc = rng.choice(LONG_APP, P)
+        ni = rng.choice(LONG_INIT, P)
+    else:
+        nc = rng.integers(1, 4, P)
+        ni = rng.choice([0, 0, 1, 2, 3], P)
     pod_ptr = np.zeros(P + 1, np.int64)
     pod_ptr[1:] = np.cumsum(nc)
     init_ptr = np.zeros(P + 1, np.int64)
@@ -37,10 +49,17 @@ def pods_case(seed, n_nodes=300, mean_pods=6, extremes=False):
     icpu = rng.integers(0, 80, I).astype(np.uint64) * np.uint64(50)
     imem = rng.integers(0, 256, I).astype(np.int64) << 26
     rst = (rng.random(I) < 0.3).astype(np.uint8)
+    if long_pods:
+        for p in np.flatnonzero((rng.random(P) < 0.33) & (ni >= 3)):
+            a, k = int(init_ptr[p]), int(ni[p])
+            lead, trail = int(rng.integers(1, k - 1)), int(rng.integers(1, k - 1))
+            rst[a:a + k] = 0
+            rst[a:a + lead] = 1                        # sidecars, then regular init containers,
+            rst[a + k - min(trail, k - lead - 1):a + k] = 1  # then sidecars again
     ocpu = np.where(rng.random(P) < 0.2, rng.integers(0, 500, P), 0).astype(np.uint64)
     omem = np.where(rng.random(P) < 0.2, rng.integers(0, 1 << 28, P), 0).astype(np.int64)
     if extremes:  # wrapping sums, sign flips of the memory max, huge cpu
-        k = rng.choice(C, 20, replace=False)
+        k = rng.choice(C, min(C, 20), replace=False)
         cpu[k[:10]] = np.uint64(U64 - 7)
         mem[k[10:]] = np.int64(-(1 << 62))
         if I:
@@ -74,6 +93,12 @@ HAND = [
     ([(U64 - 1, 0)], [(5, 0, 0)], None, (U64 - 1, 0)),                   # unsigned max
     ([(U64 - 1, 0), (3, 0)], [], None, (2, 0)),                          # wrapping sum
     ([], [(70, 7, 0)], None, (70, 7)),                                   # no app containers
+    # 5 and 9 app containers: a second and a third load batch of four, each with one live slot
+    ([(1, 10), (2, 20), (4, 40), (8, 80), (16, 160)], [], None, (31, 310)),
+    ([(1 << k, 3 << k) for k in range(9)], [(500, 1600, 0)], None, (511, 1600)),
+    # 5 init containers, a sidecar third: init = max(100, 200, 300 + 50, 400 + 50) = 450 cpu,
+    # max(1, 2, 30 + 7, 4 + 7) = 37 memory; app = 20 + 50 cpu, 5 + 7 memory
+    ([(20, 5)], [(100, 1, 0), (200, 2, 0), (50, 7, 1), (300, 30, 0), (400, 4, 0)], None, (450, 37)),
 ]
 
 
@@ -95,9 +120,12 @@ def test_oracles_hand_cases(app, init, ovh, want):
     assert pyoracle.pod_requests(**a)[0] == want
 
 
-@pytest.mark.parametrize("seed,extremes", [(1, False), (2, True), (3, True)])
-def test_c_oracle_matches_python_oracle(seed, extremes):
-    c = pods_case(seed, n_nodes=60, extremes=extremes)
+@pytest.mark.parametrize("seed,extremes,long_pods",
+                         [(1, False, False), (2, True, False), (3, True, False),
+                          (4, False, True), (5, True, True)],
+                         ids=["1-False", "2-True", "3-True", "4-False-long", "5-True-long"])
+def test_c_oracle_matches_python_oracle(seed, extremes, long_pods):
+    c = pods_case(seed, n_nodes=60, extremes=extremes, long_pods=long_pods)
     pc, pm = coracle.pod_requests(**_pod_kw(c))
     py = pyoracle.pod_requests(**_pod_kw(c))
     assert [(int(a), int(b)) for a, b in zip(pc, pm)] == py
@@ -143,6 +171,45 @@ def test_gpu_pod_requests_match_oracle(eng, seed, n_nodes, extremes):
     uc, um = eng.reduce_requests_pods(**c)
     nuc, num, _, _ = coracle.reduce_requests(c["node_pod_ptr"], oc, om)
     assert np.array_equal(uc, nuc) and np.array_equal(um, num)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extremes", [False, True])
+@pytest.mark.parametrize("P", [1, 255, 256, 257, 513])
+def test_gpu_long_pods_match_oracle(eng, P, extremes):
+    """Pods of 0 to 64 app containers and 0 to 9 init containers (whole load batches, batches
+    with one live slot, none at all), P pods around the 256-pod workgroup, through the host
+    form and kcc_pod_requests_async."""
+    import torch
+    c = pods_case(20 + P, long_pods=True, extremes=extremes, n_pods=P)
+    assert c["pod_ptr"].size == P + 1
+    oc, om = coracle.pod_requests(**_pod_kw(c))
+    pc, pm = eng.pod_requests(**_pod_kw(c))
+    assert np.array_equal(pc, oc) and np.array_equal(pm, om)
+    dev = torch.device("cuda", 0)
+    t = {k: torch.from_numpy(v.view(np.int64) if v.dtype == np.uint64 else v).to(dev)
+         for k, v in _pod_kw(c).items()}
+    dc = torch.full((P,), 77, dtype=torch.int64, device=dev)
+    dm = torch.full((P,), 77, dtype=torch.int64, device=dev)
+    eng.pod_requests_async(t["pod_ptr"], t["cpu_req"], t["mem_req"], dc, dm, t["init_ptr"],
+                           t["init_cpu"], t["init_mem"], t["restartable"], t["ovh_cpu"],
+                           t["ovh_mem"])
+    torch.cuda.synchronize()
+    assert np.array_equal(dc.cpu().numpy().view(np.uint64), oc)
+    assert np.array_equal(dm.cpu().numpy(), om)
+
+
+def test_long_pods_case_holds_the_listed_shapes():
+    """(No GPU.)  The long-pod cases carry every container count of LONG_APP and LONG_INIT,
+    and sidecar runs on both sides of regular init containers."""
+    c = pods_case(20 + 513, long_pods=True, n_pods=513)
+    assert set(np.diff(c["pod_ptr"]).tolist()) == set(LONG_APP)
+    assert set(np.diff(c["init_ptr"]).tolist()) == set(LONG_INIT)
+    both = 0
+    for p in range(513):
+        r = c["restartable"][c["init_ptr"][p]:c["init_ptr"][p + 1]].tolist()
+        both += len(r) >= 3 and r[0] == 1 and r[-1] == 1 and 0 in r
+    assert both >= 10
 
 
 @pytest.mark.gpu

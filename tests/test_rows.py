@@ -55,6 +55,23 @@ def test_gpu_rows_match_oracle(eng, spec):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1025])
+def test_gpu_rows_match_oracle_small(eng, n):
+    """Row counts around the 64-lane wave and the 256-thread workgroup: every row of the
+    adversarial cluster (tests/test_groups.py rows_case) under an ordinary spec and under
+    (2^64 - 1, -1), q and err compared row by row."""
+    from tests.test_groups import rows_case as any_n_rows
+    rows = any_n_rows(n)
+    for sc, sm in [(200, 262_144_000), (U64 - 1, -1)]:
+        q, err = eng.max_replicas_per_row(*rows, sc, sm)
+        assert q.shape == err.shape == (n,)
+        for i in range(n):
+            oq, oz = coracle.fit_one(*[int(a[i]) for a in rows], sc, sm)
+            assert int(err[i]) == oz, (n, i)
+            assert int(q[i]) == (0 if oz else oq), (n, i)
+
+
+@pytest.mark.gpu
 def test_gpu_rows_empty(eng):
     q, err = eng.max_replicas_per_row([], [], [], [], [], [], 1, 1)
     assert q.size == 0 and err.size == 0
