@@ -18,6 +18,14 @@
 // -byPool (the pools' totals under the per-node cap) and -extRequests; the totals then come
 // from kcc_fit_capped and kcc_spread_fold, and with -spreadBy zone "Zone <name> : <used> of
 // <cap>" lines follow the total.  Without them the output is the reference's.
+// -deploy <file> (opt-in): a rollout plan placed on the nodes before every fit, one step per
+// line, "cpuRequests memRequests replicas [pack|spread] [perNode:k] [name=amount ...]" ('#'
+// comments as in a -specs file), in file order through kcc_deploy (consecutive lines of one
+// policy share a call).  After the echo line (CC:85) each step prints "Deployed <cpu> <mem>
+// <replicas> : <placed> on <nodes> nodes"; a step on which Go would panic prints the
+// reference's panic line and exits with status 2.  Every later number — the total, -specs,
+// -byPool, -maxPerNode, -spreadBy zone — then comes from the updated sums and pod counts.  -v
+// with -deploy is refused (the verbose report recomputes its own sums).
 #include <array>
 #include <cctype>
 #include <cerrno>
@@ -52,7 +60,7 @@ struct Flags {
       {"replicas", "1"},          {"specs", ""},            {"device", "0"},
       {"gpus", "1"},              {"v", "false"},           {"schedulerRequests", "false"},
       {"byPool", "false"},        {"extRequests", ""},      {"maxPerNode", "0"},
-      {"spreadBy", ""},           {"maxSkew", "1"}};
+      {"spreadBy", ""},           {"maxSkew", "1"},         {"deploy", ""}};
 };
 
 // Go flag package syntax: -name=value, -name value, --name=value; bool -v.
@@ -91,6 +99,7 @@ bool parseFlags(int argc, char** argv, Flags& f) {
 }
 
 using NameAmount = std::vector<std::pair<std::string, std::string>>;
+bool goAtoiStrict(const std::string& s, int64_t& out);
 
 struct Spec {
   std::string cpuStr, memStr, repStr;
@@ -129,6 +138,48 @@ bool readSpecFile(const std::string& path, std::vector<Spec>& out) {
     out.push_back(s);
   }
   return true;
+}
+
+// One line of a -deploy file: a spec, the policy and the per-node cap (0: none).
+struct Step {
+  Spec spec;
+  int policy = KCC_DEPLOY_PACK;
+  int64_t perNode = 0;
+};
+
+// The steps of a -deploy file as strings.  0: read; 1: cannot open; 2: a token after the three
+// columns that is neither pack, spread, perNode:<count> nor name=amount (bad holds it).
+int readDeployFile(const std::string& path, std::vector<Step>& out, std::string& bad) {
+  std::ifstream sf(path);
+  if (!sf) return 1;
+  std::string line;
+  while (std::getline(sf, line)) {
+    std::istringstream is(line);
+    Step st;
+    Spec& s = st.spec;
+    if (!(is >> s.cpuStr >> s.memStr >> s.repStr) || s.cpuStr[0] == '#') continue;
+    std::string tok;
+    while (is >> tok && tok[0] != '#') {
+      const size_t eq = tok.find('=');
+      if (tok == "pack") {
+        st.policy = KCC_DEPLOY_PACK;
+      } else if (tok == "spread") {
+        st.policy = KCC_DEPLOY_SPREAD;
+      } else if (tok.compare(0, 8, "perNode:") == 0) {
+        if (!goAtoiStrict(tok.substr(8), st.perNode) || st.perNode < 0) {
+          bad = tok;
+          return 2;
+        }
+      } else if (eq != std::string::npos && eq != 0 && eq + 1 != tok.size()) {
+        s.ext.emplace_back(tok.substr(0, eq), tok.substr(eq + 1));
+      } else {
+        bad = tok;
+        return 2;
+      }
+    }
+    out.push_back(st);
+  }
+  return 0;
 }
 
 // The extended resources of a run: the union of the names the specs request, in
@@ -319,6 +370,27 @@ int main(int argc, char** argv) {
   const bool byZone = f.v["spreadBy"] == "zone";
   const bool spread = byZone || maxPerNode > 0;
 
+  // opt-in rollout plan (NOT the reference's arithmetic): its steps as strings
+  const bool deployOn = !f.v["deploy"].empty();
+  std::vector<Step> plan;
+  if (deployOn) {
+    if (verbose) {
+      std::fprintf(stderr, "-v cannot be combined with -deploy: the per-node report recomputes its own sums\n");
+      return 2;
+    }
+    std::string bad;
+    const int drc = readDeployFile(f.v["deploy"], plan, bad);
+    if (drc == 1) {
+      std::fprintf(stderr, "cannot open deploy file %s\n", f.v["deploy"].c_str());
+      return 1;
+    }
+    if (drc == 2) {
+      std::fprintf(stderr, "invalid token \"%s\" in deploy file %s: want pack, spread, perNode:<count> or name=amount\n",
+                   bad.c_str(), f.v["deploy"].c_str());
+      return 2;
+    }
+  }
+
   Spec one{f.v["cpuRequests"], f.v["memRequests"], f.v["replicas"], 0, 0, 0, {}};
   if (!parseExtList(f.v["extRequests"], one.ext)) {
     std::fprintf(stderr, "invalid value \"%s\" for flag -extRequests: want name=amount[,name=amount...]\n",
@@ -338,6 +410,14 @@ int main(int argc, char** argv) {
   ExtRun ext;
   bool useExt = false;
   for (const Spec& s : specs) useExt = useExt || !s.ext.empty();
+  // the plan's resource names count towards KCC_EXT_MAX with the specs': one name list, the
+  // specs' columns first (ext.spec_x [R * S]), then the steps' (plan_x [R * K])
+  std::vector<Spec> named(specs);
+  for (const Step& st : plan) {
+    useExt = useExt || !st.spec.ext.empty();
+    named.push_back(st.spec);
+  }
+  std::vector<int64_t> plan_x;
   const std::string path = !f.v["cluster"].empty() ? f.v["cluster"] : f.v["kubeconfig"];
   if (useExt) {
     std::string err;
@@ -351,10 +431,20 @@ int main(int argc, char** argv) {
     }
     const int rc = kcc_create(&ctx, std::atoi(f.v["device"].c_str()), std::atoi(f.v["gpus"].c_str()));
     if (rc) return fail(nullptr, rc);
-    if (!loadExt(ctx, specs, cl, ext, err)) {
+    if (!loadExt(ctx, named, cl, ext, err)) {
       std::fprintf(stderr, "%s\n", err.c_str());
       kcc_destroy(ctx);
       return 1;
+    }
+    if (deployOn) {  // split the columns: the specs', the steps'
+      const size_t R = (size_t)ext.R(), S0 = specs.size(), K = plan.size();
+      const std::vector<int64_t> all(ext.spec_x);
+      ext.spec_x.assign(R * S0, 0);
+      plan_x.assign(R * K, 0);
+      for (size_t r = 0; r < R; ++r) {
+        for (size_t s = 0; s < S0; ++s) ext.spec_x[r * S0 + s] = all[r * (S0 + K) + s];
+        for (size_t k = 0; k < K; ++k) plan_x[r * K + k] = all[r * (S0 + K) + S0 + k];
+      }
     }
   }
   const uint64_t cpuLimits = convertCPUToMilis(f.v["cpuLimits"]);            // CC:65
@@ -378,6 +468,7 @@ int main(int argc, char** argv) {
   } else {
     specs[0] = one;  // (parsed above, CC:64-83)
   }
+  for (Step& st : plan) parseSpec(st.spec, false);
 
   // cluster access (CC:88-99): a cluster file replaces kubeconfig + client-go
   if (path.empty()) {
@@ -434,6 +525,56 @@ int main(int argc, char** argv) {
     }
   }
   const int64_t S = (int64_t)specs.size();
+
+  // -deploy: the plan's steps on the per-node sums and pod counts, in file order; every fit
+  // below then reads the updated state (suc / sum_ / euc / eum, in.pod_count, ext.used_x) as
+  // the -schedulerRequests path reads its explicit sums
+  const bool explicitSums = schedReq || deployOn;
+  if (deployOn) {
+    if (!schedReq && !useExt) {  // the per-node request sums (CC:290-293)
+      euc.assign((size_t)n, 0);
+      eum.assign((size_t)n, 0);
+      rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(), in.mem_req.data(),
+                               nullptr, nullptr, euc.data(), eum.data(), nullptr, nullptr);
+      if (rc) return fail(ctx, rc);
+    }
+    const size_t K = plan.size(), R = (size_t)ext.R();
+    for (size_t k0 = 0; k0 < K;) {
+      size_t k1 = k0 + 1;
+      while (k1 < K && plan[k1].policy == plan[k0].policy) ++k1;
+      const size_t kn = k1 - k0;
+      std::vector<uint64_t> pc(kn);
+      std::vector<int64_t> pm(kn), prep(kn), pcap(kn), px(R * kn), placed(kn), used(kn);
+      std::vector<int32_t> perr(kn);
+      for (size_t k = 0; k < kn; ++k) {
+        const Step& st = plan[k0 + k];
+        pc[k] = st.spec.cpu;
+        pm[k] = st.spec.mem;
+        prep[k] = st.spec.replicas;
+        pcap[k] = st.perNode;
+        for (size_t r = 0; r < R; ++r) px[r * kn + k] = plan_x[r * K + k0 + k];
+      }
+      rc = kcc_deploy(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                      ext.R(), ext.alloc_x.data(), in.pod_count.data(), euc.data(), eum.data(),
+                      ext.used_x.data(), nullptr, 1, nullptr, (int64_t)kn, pc.data(), pm.data(),
+                      px.data(), prep.data(), pcap.data(), plan[k0].policy, placed.data(),
+                      used.data(), perr.data(), nullptr);
+      if (rc) return fail(ctx, rc);
+      for (size_t k = 0; k < kn; ++k) {
+        const Spec& s = plan[k0 + k].spec;
+        if (perr[k]) {
+          std::fprintf(stderr, "panic: runtime error: integer divide by zero\n");
+          kcc_destroy(ctx);
+          return 2;
+        }
+        std::printf("Deployed %s %s %s : %" PRId64 " on %" PRId64 " nodes\n", s.cpuStr.c_str(),
+                    s.memStr.c_str(), s.repStr.c_str(), placed[k], used[k]);
+      }
+      k0 = k1;
+    }
+    suc = euc;
+    sum_ = eum;
+  }
 
   if (verbose) {  // CC:107-117, 137 — per-node sums and fit, one row at a time
     std::vector<uint64_t> uc(n), lc(n);
@@ -501,7 +642,7 @@ int main(int argc, char** argv) {
                      in.pod_count.data(), euc.data(), eum.data(), ext.R(), ext.alloc_x.data(),
                      ext.used_x.data(), nullptr, 1, S, sc.data(), sm.data(), ext.spec_x.data(),
                      totals.data(), serr.data());
-  else if (schedReq)
+  else if (explicitSums)
     rc = kcc_fit(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
                  in.pod_count.data(), suc.data(), sum_.data(), (int64_t)specs.size(), sc.data(),
                  sm.data(), totals.data(), serr.data());
@@ -537,7 +678,7 @@ int main(int argc, char** argv) {
     const int64_t Z = byZone ? (int64_t)zones.size() : 1;
     std::vector<uint64_t> uc(useExt ? euc : suc);
     std::vector<int64_t> um(useExt ? eum : sum_);
-    if (!useExt && !schedReq) {  // the per-node request sums (CC:290-293)
+    if (!useExt && !explicitSums) {  // the per-node request sums (CC:290-293)
       uc.resize((size_t)n);
       um.resize((size_t)n);
       rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(),
@@ -597,7 +738,7 @@ int main(int argc, char** argv) {
     }
     std::vector<uint64_t> uc(suc);
     std::vector<int64_t> um(sum_);
-    if (!schedReq) {  // the per-node request sums (CC:290-293) the grouped fit takes
+    if (!explicitSums) {  // the per-node request sums (CC:290-293) the grouped fit takes
       uc.resize((size_t)n);
       um.resize((size_t)n);
       rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(),

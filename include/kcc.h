@@ -595,6 +595,84 @@ int kcc_spread_fold_async(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs,
                           int64_t* d_totals, int32_t* d_spec_err, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * A rollout plan placed on the nodes before the fit.  Every fit above answers "how many
+ * replicas of one spec fit into the cluster as it stands"; its S specs are S independent
+ * what-ifs.  "We roll out 40 of A and 200 of B; what fits after that, and where did they
+ * land?" is sequential: kcc_deploy commits a plan of K steps to the node rows, in order, and
+ * leaves the node state (on the device, in the async form) for the fit that follows.  OPT-IN,
+ * not the reference's arithmetic; no other entry point changes.
+ *
+ *   Node arrays as kcc_fit_ext's: alloc_cpu, alloc_mem, alloc_pods, n_ext = R, alloc_x [R * N].
+ *   State, updated in place: pod_count [N], used_cpu [N], used_mem [N], used_x [R * N].
+ *   group [N] (nullable: n_groups must be 1, every row in group 0), n_groups = G and
+ *     eligible [g * K + k] (uint8, nullable: every group eligible; the fold's convention with K
+ *     in place of S): row i is eligible for step k iff group[i] is in [0, G) and its group's
+ *     byte is nonzero.
+ *   The plan: spec_cpu [K], spec_mem [K], spec_x [R * K], replicas [K], node_cap [K] (nullable;
+ *     <= 0: no cap).  policy: KCC_DEPLOY_PACK or KCC_DEPLOY_SPREAD, one per call (a plan of
+ *     mixed policies is several calls on one stream).
+ *   Outputs: placed [K], nodes_used [K] (int64), step_err [K] (int32), placed_rows [K * N]
+ *     (int64, nullable).
+ *
+ * Steps k = 0 .. K - 1 run in order; each sees the state the earlier steps left:
+ *     Rk = clamp(replicas[k], 0, 2^31 - 1)
+ *     for each eligible row i: q_i as kcc_fit_ext's for row i and spec k on the current state,
+ *       up to and including the pod-slot clamp (CC:134-136, after all the mins); z_i = kcc_fit's
+ *       divide-by-zero rule for that row
+ *     if any eligible row has z_i: step_err[k] = KCC_SPEC_DIVZERO, placed[k] = nodes_used[k] = 0,
+ *       its placed_rows 0, the state untouched; the next step runs.  An ineligible row never
+ *       raises the flag.
+ *     else a_i = 0 for an ineligible row; for an eligible one max(q_i, 0) (a negative clamp
+ *       value holds nothing), then at most node_cap[k] where node_cap[k] > 0 (after the clamp, as
+ *       kcc_fit_capped's), then at most Rk.  T = sum of a_i (< 2^62: nothing wraps).
+ *     the placement p_i:
+ *       Rk >= T: p_i = a_i.  Rk == 0: p_i = 0.
+ *       PACK:   p_i = min(a_i, max(0, Rk - sum of a_j over j < i)): first fit in row order, the
+ *               reference's own node order (CC:105)
+ *       SPREAD (1 <= Rk < T): t = the smallest t >= 1 with sum of min(a_i, t) >= Rk;
+ *               b_i = min(a_i, t - 1), rem = Rk - sum of b_i (1 <= rem <= #{a_i >= t}); the first
+ *               rem rows in row order with a_i >= t get b_i + 1, every other row b_i: the even
+ *               fill, each replica into an emptiest node that has room
+ *     commit (wrapping as the reference's sums; with sane inputs nothing wraps):
+ *       used_cpu[i] += p_i * spec_cpu[k] (uint64), used_mem[i] += p_i * spec_mem[k] (int64),
+ *       used_x[r][i] += p_i * spec_x[r][k] for each requested r (a zero request leaves used_x[r]
+ *       alone), pod_count[i] += p_i
+ *     placed[k] = sum of p_i, nodes_used[k] = #{p_i > 0}, step_err[k] = KCC_SPEC_OK.
+ *
+ * Argument errors and size limits are kcc_fit_ext's with K in place of S (n_groups * K <= 2^28,
+ * n_nodes <= 2^31 - 4096, K <= 2^20); a policy outside {0, 1}: KCC_EINVAL.  K == 0 or
+ * n_nodes == 0: KCC_OK, outputs 0, the state untouched.  The host form runs on the context's
+ * device 0, retains no caller pointer and writes the four state arrays back.  The async form
+ * takes device pointers and only enqueues: it allocates only when a size exceeds every earlier
+ * call's, never synchronises and never reads a device value on the host (the plan's values are
+ * read on the device by index k); the number and kind of its launches depend only on (N, K, R,
+ * policy), so it can be captured into a hipGraph with the kcc_fit*_async call that follows it.
+ * No kernel of it waits on another workgroup: it neither sets nor reads the fault words.
+ * ------------------------------------------------------------------------- */
+#define KCC_DEPLOY_PACK 0
+#define KCC_DEPLOY_SPREAD 1
+int kcc_deploy(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+               const int64_t* alloc_pods, int64_t n_ext, const int64_t* alloc_x /* [R * N] */,
+               int64_t* pod_count, uint64_t* used_cpu, int64_t* used_mem,
+               int64_t* used_x /* [R * N] */, const int32_t* group /* nullable */,
+               int64_t n_groups, const uint8_t* eligible /* [G * K], nullable */, int64_t n_steps,
+               const uint64_t* spec_cpu, const int64_t* spec_mem,
+               const int64_t* spec_x /* [R * K] */, const int64_t* replicas,
+               const int64_t* node_cap /* [K], nullable */, int policy, int64_t* placed /* [K] */,
+               int64_t* nodes_used /* [K] */, int32_t* step_err /* [K] */,
+               int64_t* placed_rows /* [K * N], nullable */);
+int kcc_deploy_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                     const int64_t* d_alloc_mem, const int64_t* d_alloc_pods, int64_t n_ext,
+                     const int64_t* d_alloc_x, int64_t* d_pod_count, uint64_t* d_used_cpu,
+                     int64_t* d_used_mem, int64_t* d_used_x, const int32_t* d_group,
+                     int64_t n_groups, const uint8_t* d_eligible, int64_t n_steps,
+                     const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                     const int64_t* d_spec_x, const int64_t* d_replicas,
+                     const int64_t* d_node_cap, int policy, int64_t* d_placed,
+                     int64_t* d_nodes_used, int32_t* d_step_err, int64_t* d_placed_rows,
+                     void* stream);
+
+/* ---------------------------------------------------------------------------
  * OPT-IN scheduler request model — explicitly NOT the
  * reference's semantics: the reference sums only the app containers of a node's pods
  * (CC:276-294, kcc_reduce_requests above; that stays the default).  This gives the

@@ -6,9 +6,11 @@ include/kcc.h).  Importing this package does not touch the GPU; constructing a
 CapacityEngine loads libkcc.so and fails loudly if it is missing.
 """
 from ._lib import KCC_EXT_MAX  # noqa: F401  (extra resources of CapacityEngine.fit_ext)
-from .engine import CapacityEngine, KccError, RequestSums, select_groups, verdict  # noqa: F401
+from ._lib import KCC_DEPLOY_PACK, KCC_DEPLOY_SPREAD  # noqa: F401  (CapacityEngine.deploy)
+from .engine import (CapacityEngine, DeployResult, KccError, RequestSums,  # noqa: F401
+                     select_groups, verdict)
 from .shard import node_range, shard_bounds  # noqa: F401
 
-__all__ = ["CapacityEngine", "KccError", "RequestSums", "verdict", "select_groups",
-           "node_range",
-           "shard_bounds", "KCC_EXT_MAX"]
+__all__ = ["CapacityEngine", "KccError", "RequestSums", "DeployResult", "verdict",
+           "select_groups", "node_range",
+           "shard_bounds", "KCC_EXT_MAX", "KCC_DEPLOY_PACK", "KCC_DEPLOY_SPREAD"]

@@ -29,6 +29,12 @@ KCC_SPEC_OK = 0
 KCC_SPEC_DIVZERO = 1
 KCC_SPEC_FAULT = 2
 KCC_EXT_MAX = 4  # include/kcc.h: extra resources of kcc_fit_ext
+# kcc_deploy (include/kcc.h): the policies; csrc/kcc_internal.h: the rows of one tile of its
+# row pass (DEPLOY_TILE) and the tile sums one pass of its scan takes (DEPLOY_SCAN_PASS)
+KCC_DEPLOY_PACK = 0
+KCC_DEPLOY_SPREAD = 1
+KCC_DEPLOY_TILE = 1024
+KCC_DEPLOY_SCAN_PASS = 256
 
 _i64, _i32, _int, _vp, _dbl = C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_double
 
@@ -94,6 +100,10 @@ SIGNATURES = {
                              + [_vp] * 9),
     "kcc_spread_fold": (_int, [_vp, _i64, _i64] + [_vp] * 4 + [_i64] + [_vp] * 4),
     "kcc_spread_fold_async": (_int, [_vp, _i64, _i64] + [_vp] * 4 + [_i64] + [_vp] * 5),
+    "kcc_deploy": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64, _vp, _i64]
+                   + [_vp] * 5 + [_int] + [_vp] * 4),
+    "kcc_deploy_async": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64, _vp, _i64]
+                         + [_vp] * 5 + [_int] + [_vp] * 5),
     "kcc_pod_requests": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 11),
     "kcc_pod_requests_async": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 12),
     "kcc_reduce_requests_pods": (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 12),

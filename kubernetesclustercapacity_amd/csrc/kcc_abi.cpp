@@ -113,6 +113,8 @@ struct Dev {
   DevBuf sp_cap, sp_cmin, sp_grows;  // kcc_fit_capped staging (node_cap; cell_min, group_rows)
   DevBuf f_cap, f_present, f_flag;   // kcc::FoldWork (kcc_spread_fold)
   DevBuf f_ct, f_ce, f_gr, f_dom, f_el, f_skew;  // kcc_spread_fold staging
+  DevBuf dp_a, dp_tsum, dp_toff, dp_flag, dp_st, dp_bins;  // kcc::DeployWork (kcc_deploy)
+  DevBuf dp_el, dp_rep, dp_nused, dp_rows;  // kcc_deploy staging (eligible, replicas; outputs)
   DevBuf kb_counts, kb_tot, kb_sr, kb_sv;  // kcc::KeyedWork (bucketed keyed reduce)
   DevBuf kb_part, kb_arrive;               // one-sweep gather: part rows, arrivals (zeroed)
   DevBuf kb_esc_n, kb_esc_row, kb_esc_cpu, kb_esc_mem;
@@ -1031,7 +1033,9 @@ void kcc_destroy(kcc_ctx* ctx) {
                       &dv.g_rg,      &dv.g_acc,     &dv.x_alloc,   &dv.x_used,    &dv.x_spec,
                       &dv.x_rec,     &dv.sp_qmin,   &dv.sp_cap,    &dv.sp_cmin,   &dv.sp_grows,
                       &dv.f_cap,     &dv.f_present, &dv.f_flag,    &dv.f_ct,      &dv.f_ce,
-                      &dv.f_gr,      &dv.f_dom,     &dv.f_el,      &dv.f_skew};
+                      &dv.f_gr,      &dv.f_dom,     &dv.f_el,      &dv.f_skew,
+                      &dv.dp_a,      &dv.dp_tsum,   &dv.dp_toff,   &dv.dp_flag,   &dv.dp_st,
+                      &dv.dp_bins,   &dv.dp_el,     &dv.dp_rep,    &dv.dp_nused,  &dv.dp_rows};
     for (DevBuf* b : bufs)
       if (b->p) (void)hipFree(b->p);
     if (dv.stream) (void)hipStreamDestroy(dv.stream);
@@ -2183,6 +2187,176 @@ int kcc_spread_fold(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs, const int64
                               dv.stream));
   KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * (size_t)n_specs, hipMemcpyDeviceToHost,
                               dv.stream));
+  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
+  return KCC_OK;
+}
+
+}  // extern "C"
+
+
+// ---- a rollout plan committed to the node rows (kcc_deploy.hip) -------------------------
+
+namespace {
+
+struct DeployArgs {
+  kcc::FitNodes nd;  // pod_count / used_* left nullptr: the state is the four pointers below
+  int64_t* pod_count;
+  uint64_t* used_cpu;
+  int64_t* used_mem;
+  int64_t* used_x;
+  const uint8_t* eligible;
+  kcc::DeployPlan plan;
+  int64_t* placed;
+  int64_t* nodes_used;
+  int32_t* step_err;
+  int64_t* placed_rows;
+};
+
+// Argument checks of both entry points (host or device pointers alike).
+int check_deploy(kcc_ctx* ctx, const DeployArgs& a) {
+  const kcc::FitNodes& nd = a.nd;
+  const int64_t K = a.plan.K;
+  if (nd.n < 0 || K < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (a.plan.policy != KCC_DEPLOY_PACK && a.plan.policy != KCC_DEPLOY_SPREAD)
+    return fail(ctx, KCC_EINVAL, "policy must be KCC_DEPLOY_PACK or KCC_DEPLOY_SPREAD");
+  if (nd.R < 0 || nd.R > KCC_EXT_MAX) return fail(ctx, KCC_EINVAL, "n_ext must be in [0, KCC_EXT_MAX]");
+  if (nd.G < 1) return fail(ctx, KCC_EINVAL, "n_groups must be at least 1");
+  if (!nd.group && nd.G != 1) return fail(ctx, KCC_EINVAL, "group is NULL: n_groups must be 1");
+  if (nd.n > kcc::GRP_MAX_NODES) return fail(ctx, KCC_EINVAL, "too many nodes (max 2^31 - 4096)");
+  if (K > kcc::DEPLOY_MAX_STEPS) return fail(ctx, KCC_EINVAL, "too many steps (max 2^20)");
+  if (nd.G > kcc::GRP_MAX_CELLS || nd.G * K > kcc::GRP_MAX_CELLS)
+    return fail(ctx, KCC_EINVAL, "too many cells: n_groups x n_steps must not exceed 2^28");
+  if (K > 0 && (!a.plan.spec_cpu || !a.plan.spec_mem || !a.plan.replicas || !a.placed ||
+                !a.nodes_used || !a.step_err))
+    return fail(ctx, KCC_EINVAL, "NULL plan array / output");
+  if (nd.n > 0 && (!nd.alloc_cpu || !nd.alloc_mem || !nd.alloc_pods || !a.pod_count ||
+                   !a.used_cpu || !a.used_mem))
+    return fail(ctx, KCC_EINVAL, "NULL node array");
+  if (nd.R > 0 && ((nd.n > 0 && (!nd.alloc_x || !a.used_x)) || (K > 0 && !a.plan.spec_x)))
+    return fail(ctx, KCC_EINVAL, "NULL extra-resource array with n_ext > 0");
+  return KCC_OK;
+}
+
+// Device level: the workspaces (they only grow) and the launches on s.  n, K >= 1.
+int deploy_dev(kcc_ctx* ctx, Dev& dv, const DeployArgs& a, hipStream_t s) {
+  const size_t tiles = (size_t)kcc::deploy_tiles(a.nd.n), K = (size_t)a.plan.K;
+  KCC_HIP(ctx, ensure(dv.dp_a, 4 * (size_t)a.nd.n));
+  KCC_HIP(ctx, ensure(dv.dp_tsum, 8 * tiles));
+  KCC_HIP(ctx, ensure(dv.dp_toff, 8 * tiles));
+  KCC_HIP(ctx, ensure(dv.dp_flag, 4 * K * kcc::DEPLOY_FLAG_STRIDE));
+  KCC_HIP(ctx, ensure(dv.dp_st, 8 * K * 4 * kcc::DEPLOY_ST_WORDS));
+  if (a.plan.policy == KCC_DEPLOY_SPREAD)
+    KCC_HIP(ctx, ensure(dv.dp_bins, 8 * K * (size_t)kcc::DEPLOY_BIN_WORDS));
+  const kcc::DeployWork w{as<uint32_t>(dv.dp_a),    as<uint64_t>(dv.dp_tsum), as<uint64_t>(dv.dp_toff),
+                          as<uint32_t>(dv.dp_flag), as<uint64_t>(dv.dp_st),   as<uint64_t>(dv.dp_bins)};
+  KCC_HIP(ctx, kcc::launch_deploy(a.nd, a.pod_count, a.used_cpu, a.used_mem, a.used_x, a.eligible,
+                                  a.plan, w, a.placed, a.nodes_used, a.step_err, a.placed_rows, s));
+  return KCC_OK;
+}
+
+template <class T>
+int d2h(kcc_ctx* ctx, Dev& dv, T* dst, const DevBuf& buf, int64_t count) {
+  if (count > 0)
+    KCC_HIP(ctx, hipMemcpyAsync(dst, buf.p, sizeof(T) * (size_t)count, hipMemcpyDeviceToHost,
+                                dv.stream));
+  return KCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kcc_deploy_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                     const int64_t* d_alloc_mem, const int64_t* d_alloc_pods, int64_t n_ext,
+                     const int64_t* d_alloc_x, int64_t* d_pod_count, uint64_t* d_used_cpu,
+                     int64_t* d_used_mem, int64_t* d_used_x, const int32_t* d_group,
+                     int64_t n_groups, const uint8_t* d_eligible, int64_t n_steps,
+                     const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                     const int64_t* d_spec_x, const int64_t* d_replicas,
+                     const int64_t* d_node_cap, int policy, int64_t* d_placed,
+                     int64_t* d_nodes_used, int32_t* d_step_err, int64_t* d_placed_rows,
+                     void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  const DeployArgs a{{n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, nullptr, nullptr, nullptr,
+                      n_ext, d_alloc_x, nullptr, d_group, n_groups},
+                     d_pod_count, d_used_cpu, d_used_mem, d_used_x, d_eligible,
+                     {n_steps, d_spec_cpu, d_spec_mem, d_spec_x, d_replicas, d_node_cap, policy},
+                     d_placed, d_nodes_used, d_step_err, d_placed_rows};
+  int rc = check_deploy(ctx, a);
+  if (rc) return rc;
+  if (n_steps == 0) return KCC_OK;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_nodes == 0) {  // no rows: nothing placed, no step flagged
+    KCC_HIP(ctx, hipMemsetAsync(d_placed, 0, 8 * (size_t)n_steps, s));
+    KCC_HIP(ctx, hipMemsetAsync(d_nodes_used, 0, 8 * (size_t)n_steps, s));
+    KCC_HIP(ctx, hipMemsetAsync(d_step_err, 0, 4 * (size_t)n_steps, s));
+    return KCC_OK;
+  }
+  return deploy_dev(ctx, dv, a, s);
+}
+
+int kcc_deploy(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+               const int64_t* alloc_pods, int64_t n_ext, const int64_t* alloc_x,
+               int64_t* pod_count, uint64_t* used_cpu, int64_t* used_mem, int64_t* used_x,
+               const int32_t* group, int64_t n_groups, const uint8_t* eligible, int64_t n_steps,
+               const uint64_t* spec_cpu, const int64_t* spec_mem, const int64_t* spec_x,
+               const int64_t* replicas, const int64_t* node_cap, int policy, int64_t* placed,
+               int64_t* nodes_used, int32_t* step_err, int64_t* placed_rows) {
+  if (!ctx) return KCC_EINVAL;
+  DeployArgs a{{n_nodes, alloc_cpu, alloc_mem, alloc_pods, nullptr, nullptr, nullptr, n_ext,
+                alloc_x, nullptr, group, n_groups},
+               pod_count, used_cpu, used_mem, used_x, eligible,
+               {n_steps, spec_cpu, spec_mem, spec_x, replicas, node_cap, policy},
+               placed, nodes_used, step_err, placed_rows};
+  int rc = check_deploy(ctx, a);
+  if (rc) return rc;
+  const int64_t n = n_nodes, K = n_steps, R = n_ext;
+  if (K == 0) return KCC_OK;
+  if (n == 0) {
+    memset(placed, 0, 8 * (size_t)K);
+    memset(nodes_used, 0, 8 * (size_t)K);
+    memset(step_err, 0, 4 * (size_t)K);
+    return KCC_OK;
+  }
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  if ((rc = stage(ctx, dv, dv.alloc_cpu, a.nd.alloc_cpu, n)) ||
+      (rc = stage(ctx, dv, dv.alloc_mem, a.nd.alloc_mem, n)) ||
+      (rc = stage(ctx, dv, dv.alloc_pods, a.nd.alloc_pods, n)) ||
+      (rc = stage(ctx, dv, dv.x_alloc, a.nd.alloc_x, R * n)) ||
+      (rc = stage(ctx, dv, dv.g_group, a.nd.group, n)) ||
+      (rc = stage(ctx, dv, dv.dp_el, a.eligible, n_groups * K)) ||
+      (rc = stage(ctx, dv, dv.spec_cpu, a.plan.spec_cpu, K)) ||
+      (rc = stage(ctx, dv, dv.spec_mem, a.plan.spec_mem, K)) ||
+      (rc = stage(ctx, dv, dv.x_spec, a.plan.spec_x, R * K)) ||
+      (rc = stage(ctx, dv, dv.dp_rep, a.plan.replicas, K)) ||
+      (rc = stage(ctx, dv, dv.sp_cap, a.plan.node_cap, K)) ||
+      (rc = h2d(ctx, dv, dv.pod_count, pod_count, n)) ||
+      (rc = h2d(ctx, dv, dv.used_cpu, used_cpu, n)) ||
+      (rc = h2d(ctx, dv, dv.used_mem, used_mem, n)) ||
+      (R > 0 && (rc = h2d(ctx, dv, dv.x_used, used_x, R * n))))
+    return rc;
+  KCC_HIP(ctx, ensure(dv.totals, 8 * (size_t)K));
+  KCC_HIP(ctx, ensure(dv.dp_nused, 8 * (size_t)K));
+  KCC_HIP(ctx, ensure(dv.err, 4 * (size_t)K));
+  if (placed_rows) KCC_HIP(ctx, ensure(dv.dp_rows, 8 * (size_t)K * (size_t)n));
+  a.pod_count = as<int64_t>(dv.pod_count);
+  a.used_cpu = as<uint64_t>(dv.used_cpu);
+  a.used_mem = as<int64_t>(dv.used_mem);
+  a.used_x = R > 0 ? as<int64_t>(dv.x_used) : nullptr;
+  a.placed = as<int64_t>(dv.totals);
+  a.nodes_used = as<int64_t>(dv.dp_nused);
+  a.step_err = as<int32_t>(dv.err);
+  a.placed_rows = placed_rows ? as<int64_t>(dv.dp_rows) : nullptr;
+  if ((rc = deploy_dev(ctx, dv, a, dv.stream))) return rc;
+  if ((rc = d2h(ctx, dv, placed, dv.totals, K)) || (rc = d2h(ctx, dv, nodes_used, dv.dp_nused, K)) ||
+      (rc = d2h(ctx, dv, step_err, dv.err, K)) || (rc = d2h(ctx, dv, pod_count, dv.pod_count, n)) ||
+      (rc = d2h(ctx, dv, used_cpu, dv.used_cpu, n)) || (rc = d2h(ctx, dv, used_mem, dv.used_mem, n)) ||
+      (R > 0 && (rc = d2h(ctx, dv, used_x, dv.x_used, R * n))) ||
+      (placed_rows && (rc = d2h(ctx, dv, placed_rows, dv.dp_rows, K * n))))
+    return rc;
   KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
   return KCC_OK;
 }

@@ -874,6 +874,55 @@ hipError_t launch_spread_fold(int64_t G, int64_t S, const int64_t* cell_totals,
                               const int64_t* max_skew, const FoldWork& w, int64_t* totals,
                               int32_t* spec_err, hipStream_t s);
 
+// ---- a rollout plan committed to the node rows (kcc_deploy.hip) ------
+// Rows in tiles of DEPLOY_TILE: 256 threads x DEPLOY_IPT consecutive rows (kcc_deploy.hip).
+// The tile sums (at most 2^21 of them) are scanned by one workgroup, DEPLOY_SCAN_PASS a pass.
+constexpr int DEPLOY_IPT = 4;
+constexpr int DEPLOY_TILE = 256 * DEPLOY_IPT;  // 1024 (_lib.KCC_DEPLOY_TILE restates it)
+constexpr int DEPLOY_SCAN_PASS = 256;          // (_lib.KCC_DEPLOY_SCAN_PASS)
+constexpr int64_t DEPLOY_R_MAX = 0x7fffffff;   // replicas[k] is clamped to [0, this]
+constexpr int DEPLOY_PACK = 0, DEPLOY_SPREAD = 1;  // include/kcc.h KCC_DEPLOY_*
+constexpr int64_t DEPLOY_MAX_STEPS = (int64_t)1 << 20;
+// Per step: a flag word (an eligible row would panic), the digit search's state after each of
+// its four rounds (prefix, sum of a below it, rows above it, f at the prefix) and the four
+// rounds' 256 bins of (count, sum of a).
+constexpr int DEPLOY_FLAG_STRIDE = 16;  // uint32 words: one 64-B line per step
+constexpr int DEPLOY_ST_WORDS = 4;
+constexpr int64_t DEPLOY_BIN_WORDS = 4 * 256 * 2;
+inline int64_t deploy_tiles(int64_t n) { return (n + DEPLOY_TILE - 1) / DEPLOY_TILE; }
+struct DeployPlan {
+  int64_t K;
+  const uint64_t* spec_cpu;   // [K]
+  const int64_t* spec_mem;    // [K]
+  const int64_t* spec_x;      // [R, K]
+  const int64_t* replicas;    // [K]
+  const int64_t* node_cap;    // [K], nullable; <= 0: no cap
+  int policy;                 // DEPLOY_PACK / DEPLOY_SPREAD
+};
+struct DeployWork {
+  uint32_t* a;         // [n] what row i can take of the step at most (< 2^31)
+  uint64_t* tile_sum;  // [deploy_tiles(n)]
+  uint64_t* tile_off;  // [deploy_tiles(n)] exclusive scan of tile_sum
+  uint32_t* flag;      // [K * DEPLOY_FLAG_STRIDE]
+  uint64_t* st;        // [K][4][DEPLOY_ST_WORDS]
+  uint64_t* bins;      // [K][DEPLOY_BIN_WORDS] (DEPLOY_SPREAD alone)
+};
+// n, K, G >= 1, 0 <= R <= EXT_MAX, n <= GRP_MAX_NODES, G K <= GRP_MAX_CELLS, K <=
+// DEPLOY_MAX_STEPS.
+inline bool deploy_sizes_ok(const FitNodes& nd, int64_t K) {
+  if (nd.n <= 0 || K <= 0 || nd.G <= 0 || nd.R < 0 || nd.R > EXT_MAX || (!nd.group && nd.G != 1))
+    return false;
+  return nd.n <= GRP_MAX_NODES && K <= DEPLOY_MAX_STEPS && nd.G <= GRP_MAX_CELLS &&
+         nd.G * K <= GRP_MAX_CELLS;
+}
+// The plan's K steps on s, in order.  nd's pod_count / used_* are not read: the state arrays
+// are the four pointers after it, updated in place.  placed / nodes_used / step_err [K] are
+// written; placed_rows [K n] is nullable.  eligible [G K] uint8, nullable.
+hipError_t launch_deploy(const FitNodes& nd, int64_t* pod_count, uint64_t* used_cpu, int64_t* used_mem,
+                         int64_t* used_x, const uint8_t* eligible, const DeployPlan& plan,
+                         const DeployWork& w, int64_t* placed, int64_t* nodes_used,
+                         int32_t* step_err, int64_t* placed_rows, hipStream_t s);
+
 // ---- opt-in scheduler request model (kcc_pods.hip) ---------------
 hipError_t launch_pod_requests(int64_t n_pods, int64_t n_cont, int64_t n_init,
                                const int64_t* pod_ptr, const uint64_t* cpu_req,

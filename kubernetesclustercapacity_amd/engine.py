@@ -58,6 +58,21 @@ class RequestSums:
     memory_requests: np.ndarray
 
 
+@dataclass
+class DeployResult:
+    """What CapacityEngine.deploy returns: per step the replicas placed, the nodes that took
+    some and the flag (KCC_SPEC_*); the node state after the plan; rows[k, i] = replicas of
+    step k on row i (None unless asked for)."""
+    placed: np.ndarray
+    nodes_used: np.ndarray
+    err: np.ndarray
+    pod_count: np.ndarray
+    used_cpu: np.ndarray
+    used_mem: np.ndarray
+    used_x: np.ndarray
+    rows: np.ndarray | None
+
+
 class CapacityEngine:
     """One libkcc context (one device, or n_gpus devices with node sharding + RCCL)."""
 
@@ -370,6 +385,83 @@ class CapacityEngine:
                                              group, G, cap2, want_min=False)
         return self.spread_fold(t.reshape(G, S), e.reshape(G, S), grows, zone_of, n_zones,
                                 eligible, max_skew)
+
+    # -- a rollout plan placed on the nodes (opt-in; include/kcc.h) ----
+    def deploy(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+               spec_cpu, spec_mem, replicas, policy=_lib.KCC_DEPLOY_PACK, alloc_x=None,
+               used_x=None, spec_x=None, node_cap=None, group=None, n_groups=1, eligible=None,
+               want_rows=True) -> "DeployResult":
+        """Commits a plan of K steps to the node rows, in order: step k places up to
+        replicas[k] pods of (spec_cpu[k], spec_mem[k], spec_x[:, k]) on the eligible rows that
+        can hold them (fit_ext's per-row count after the pod-slot clamp, never negative, at
+        most node_cap[k] where that is > 0), first fit in row order (KCC_DEPLOY_PACK) or as an
+        even fill (KCC_DEPLOY_SPREAD), and adds them to pod_count / used_cpu / used_mem /
+        used_x, which the next step and the fit that follows see.  eligible: bool [G, K] or
+        [G] (None: every group); rows with a group id outside [0, n_groups) take nothing.  A
+        step on which Go would panic on an eligible row is flagged (err[k] = 1) and places
+        nothing.  The inputs are not modified: the result carries the updated state."""
+        a = [_arr(x, t) for x, t in zip((alloc_cpu, alloc_mem, alloc_pods),
+                                        (np.uint64, np.int64, np.int64))]
+        st = [np.array(x, dtype=t, order="C", copy=True)
+              for x, t in zip((pod_count, used_cpu, used_mem), (np.int64, np.uint64, np.int64))]
+        n = a[0].size
+        if group is not None:
+            group = _key32(group)
+        if any(x.shape != (n,) for x in a + st) or (group is not None and group.size != n):
+            raise ValueError("node arrays differ in length")
+        sc, sm, rep = _arr(spec_cpu, np.uint64), _arr(spec_mem, np.int64), _arr(replicas, np.int64)
+        K = sc.size
+        if sm.shape != (K,) or rep.shape != (K,):
+            raise ValueError("plan arrays differ in length")
+        ax = _arr(np.zeros((0, n)) if alloc_x is None else alloc_x, np.int64)
+        ux = np.array(np.zeros((0, n)) if used_x is None else used_x, dtype=np.int64, order="C",
+                      copy=True)
+        sx = _arr(np.zeros((0, K)) if spec_x is None else spec_x, np.int64)
+        if ax.ndim != 2 or ux.shape != ax.shape or ax.shape[1] != n:
+            raise ValueError("alloc_x and used_x must both be [R, N]")
+        R = ax.shape[0]
+        if sx.shape != (R, K):
+            raise ValueError("spec_x must be [R, K]")
+        cap = None if node_cap is None else _arr(node_cap, np.int64)
+        if cap is not None and cap.shape != (K,):
+            raise ValueError("node_cap must be [K]")
+        G = int(n_groups)
+        el = None
+        if eligible is not None:
+            m = np.asarray(eligible, bool)
+            if m.shape == (G,):
+                m = np.broadcast_to(m[:, None], (G, K))
+            if m.shape != (G, K):
+                raise ValueError("eligible must be [G, K] or [G]")
+            el = _arr(m, np.uint8)
+        placed = np.zeros(K, np.int64)
+        nodes_used = np.zeros(K, np.int64)
+        err = np.zeros(K, np.int32)
+        rows = np.zeros((K, n), np.int64) if want_rows else None
+        self._check(self._lib.kcc_deploy(
+            self._h, n, *[_p(x) for x in a], R, _p(ax), _p(st[0]), _p(st[1]), _p(st[2]), _p(ux),
+            _p(group), G, _p(el), K, _p(sc), _p(sm), _p(sx), _p(rep), _p(cap), int(policy),
+            _p(placed), _p(nodes_used), _p(err), _p(rows)))
+        return DeployResult(placed, nodes_used, err, st[0], st[1], st[2], ux, rows)
+
+    def deploy_async(self, alloc_cpu, alloc_mem, alloc_pods, n_ext, alloc_x, pod_count, used_cpu,
+                     used_mem, used_x, group, n_groups, eligible, spec_cpu, spec_mem, spec_x,
+                     replicas, node_cap, policy, placed, nodes_used, step_err, placed_rows=None,
+                     stream=None):
+        """Device form of deploy (torch tensors on the engine's device): pod_count, used_cpu,
+        used_mem and used_x (n_ext * N, resource-major) are updated in place; eligible uint8 of
+        n_groups * K elements; placed / nodes_used int64 [K], step_err int32 [K], placed_rows
+        int64 of K * N elements or None.  Only enqueues on `stream`: it can be captured into
+        one graph with the fit_*_async call that follows it.  The arguments go to the C-ABI
+        as they are (None: NULL), which validates them."""
+        n = 0 if alloc_cpu is None else alloc_cpu.numel()
+        k = 0 if spec_cpu is None else spec_cpu.numel()
+        self._check(self._lib.kcc_deploy_async(
+            self._h, n, _dp(alloc_cpu), _dp(alloc_mem), _dp(alloc_pods), int(n_ext), _dp(alloc_x),
+            _dp(pod_count), _dp(used_cpu), _dp(used_mem), _dp(used_x), _dp(group), int(n_groups),
+            _dp(eligible), k, _dp(spec_cpu), _dp(spec_mem), _dp(spec_x), _dp(replicas),
+            _dp(node_cap), int(policy), _dp(placed), _dp(nodes_used), _dp(step_err),
+            _dp(placed_rows), _stream(stream)))
 
     def capacity(self, node_ptr, cpu_req, mem_req, alloc_cpu, alloc_mem, alloc_pods, pod_count,
                  spec_cpu, spec_mem):
