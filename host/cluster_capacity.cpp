@@ -26,6 +26,13 @@
 // reference's panic line and exits with status 2.  Every later number — the total, -specs,
 // -byPool, -maxPerNode, -spreadBy zone — then comes from the updated sums and pod counts.  -v
 // with -deploy is refused (the verbose report recomputes its own sums).
+// -explain (opt-in): under each spec's result, which resource binds the nodes and what is left
+// over, from one ungrouped kcc_fit_explain call on the sums, -extRequests columns, -maxPerNode
+// cap and post--deploy state of the total it explains: "Limited by <name> : <rows> nodes,
+// <pods> replicas" per non-empty reason (cpu, memory, the extended resources by name, pods —
+// the pod-slot clamp — and perNode — the cap), then "Left over <name> : <amount>" per resource
+// (cpu in millicores with an m suffix).  Nothing for a spec on which Go would panic.  -explain
+// with -spreadBy zone is refused: a maxSkew-clipped total is not a sum over rows.
 #include <array>
 #include <cctype>
 #include <cerrno>
@@ -60,7 +67,8 @@ struct Flags {
       {"replicas", "1"},          {"specs", ""},            {"device", "0"},
       {"gpus", "1"},              {"v", "false"},           {"schedulerRequests", "false"},
       {"byPool", "false"},        {"extRequests", ""},      {"maxPerNode", "0"},
-      {"spreadBy", ""},           {"maxSkew", "1"},         {"deploy", ""}};
+      {"spreadBy", ""},           {"maxSkew", "1"},         {"deploy", ""},
+      {"explain", "false"}};
 };
 
 // Go flag package syntax: -name=value, -name value, --name=value; bool -v.
@@ -84,7 +92,8 @@ bool parseFlags(int argc, char** argv, Flags& f) {
       std::fprintf(stderr, "flag provided but not defined: -%s\n", name.c_str());
       return false;
     }
-    if ((name == "v" || name == "schedulerRequests" || name == "byPool") && !has) {
+    if ((name == "v" || name == "schedulerRequests" || name == "byPool" || name == "explain") &&
+        !has) {
       val = "true";
     } else if (!has) {
       if (i + 1 >= argc) {
@@ -369,6 +378,12 @@ int main(int argc, char** argv) {
   }
   const bool byZone = f.v["spreadBy"] == "zone";
   const bool spread = byZone || maxPerNode > 0;
+  // opt-in explanation of the total (NOT the reference's arithmetic)
+  const bool explain = f.v["explain"] == "true";
+  if (explain && byZone) {
+    std::fprintf(stderr, "-explain cannot be combined with -spreadBy zone: a total clipped by maxSkew is not a sum over the nodes\n");
+    return 2;
+  }
 
   // opt-in rollout plan (NOT the reference's arithmetic): its steps as strings
   const bool deployOn = !f.v["deploy"].empty();
@@ -765,6 +780,51 @@ int main(int argc, char** argv) {
         std::printf("Pool %s : %" PRId64 "\n", pools[g].c_str(), ptot[g * specs.size() + s]);
     }
   };
+  // -explain: the reasons and the leftovers of every spec's total in one ungrouped call, on
+  // the sums and the cap that total came from; wrows / wpods [slot][spec], left [resource][spec]
+  std::vector<int64_t> wrows, wpods, left;
+  if (explain && S > 0) {
+    std::vector<uint64_t> uc(useExt ? euc : suc);
+    std::vector<int64_t> um(useExt ? eum : sum_);
+    if (!useExt && !explicitSums) {  // the per-node request sums (CC:290-293)
+      uc.resize((size_t)n);
+      um.resize((size_t)n);
+      rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(),
+                               in.mem_req.data(), nullptr, nullptr, uc.data(), um.data(), nullptr,
+                               nullptr);
+      if (rc) return fail(ctx, rc);
+    }
+    std::vector<int64_t> et((size_t)S);
+    std::vector<int32_t> ee((size_t)S);
+    wrows.resize((size_t)(KCC_WHY_SLOTS * S));
+    wpods.resize((size_t)(KCC_WHY_SLOTS * S));
+    left.resize((size_t)((2 + ext.R()) * S));
+    rc = kcc_fit_explain(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                         in.pod_count.data(), uc.data(), um.data(), ext.R(), ext.alloc_x.data(),
+                         ext.used_x.data(), nullptr, 1, S, sc.data(), sm.data(), ext.spec_x.data(),
+                         maxPerNode > 0 ? caps.data() : nullptr, et.data(), ee.data(),
+                         wrows.data(), wpods.data(), left.data());
+    if (rc) return fail(ctx, rc);
+  }
+  auto printExplain = [&](size_t s) {
+    if (!explain || serr[s]) return;
+    for (int b = 0; b < KCC_WHY_SLOTS; ++b) {
+      const int64_t rws = wrows[(size_t)b * specs.size() + s];
+      if (rws == 0) continue;
+      const char* name = b == KCC_WHY_CPU    ? "cpu"
+                         : b == KCC_WHY_MEM  ? "memory"
+                         : b == KCC_WHY_PODS ? "pods"
+                         : b == KCC_WHY_CAP  ? "perNode"
+                                             : ext.names[(size_t)(b - KCC_WHY_EXT0)].c_str();
+      std::printf("Limited by %s : %" PRId64 " nodes, %" PRId64 " replicas\n", name, rws,
+                  wpods[(size_t)b * specs.size() + s]);
+    }
+    std::printf("Left over cpu : %" PRId64 "m\n", left[s]);
+    std::printf("Left over memory : %" PRId64 "\n", left[specs.size() + s]);
+    for (size_t r = 0; r < (size_t)ext.R(); ++r)
+      std::printf("Left over %s : %" PRId64 "\n", ext.names[r].c_str(),
+                  left[(2 + r) * specs.size() + s]);
+  };
   kcc_destroy(ctx);
 
   if (f.v["specs"].empty()) {  // CC:142-149, verbatim text
@@ -783,6 +843,7 @@ int main(int argc, char** argv) {
                   " replicas. Please try again by reducing the number of replicas or/and cpu/memory "
                   "resource requests. Exiting!!\n\n", specs[0].replicas);
     std::printf("%s\n", kRule);
+    printExplain(0);
     printZones(0);
     printPools(0);
     return 0;
@@ -795,6 +856,7 @@ int main(int argc, char** argv) {
     else
       std::printf("%s %s %s total=%" PRId64 " %s\n", specs[s].cpuStr.c_str(), specs[s].memStr.c_str(),
                   specs[s].repStr.c_str(), totals[s], totals[s] >= specs[s].replicas ? "yes" : "no");
+    printExplain(s);  // (-explain: this spec's reasons and leftovers under its line)
     printZones(s);  // (-spreadBy zone: this spec's zones under its line)
     printPools(s);  // (-byPool: this spec's pools under its line)
   }

@@ -595,6 +595,71 @@ int kcc_spread_fold_async(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs,
                           int64_t* d_totals, int32_t* d_spec_err, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * The fit explained: which resource binds each node, and what is left over.  Every fit above
+ * answers "how many replicas fit"; a planner asks next what stops them and what is stranded
+ * when they stop.  That depends on which term won each node's findMin — not a sum of anything
+ * another entry point returns.  OPT-IN, not the reference's arithmetic; no other call changes.
+ *
+ * kcc_fit_explain: kcc_fit_capped's input arguments in its order (node_cap included), then
+ * totals / spec_err [G * S] — kcc_fit_capped's, bit for bit — and three nullable outputs,
+ * plane-major (each plane an ordinary G x S cell array that kcc_spread_fold and a selector
+ * can consume):
+ *   why_rows[(b*G + g)*S + s]  rows of cell (g, s) whose reason is b          (KCC_WHY_SLOTS planes)
+ *   why_pods[(b*G + g)*S + s]  the wrapping sum of the final q over those rows
+ *   left[(c*G + g)*S + s]      what stays free once the cell holds its total: plane 0 CPU,
+ *                              1 memory, 2 + r extra resource r                (2 + n_ext planes)
+ * Reasons: KCC_WHY_CPU, KCC_WHY_MEM, KCC_WHY_EXT0 + r (r < KCC_EXT_MAX), KCC_WHY_PODS (the
+ * pod-slot clamp), KCC_WHY_CAP (node_cap).  For row i and spec s, kcc_fit_capped's arithmetic
+ * with the reason carried along; ties keep the earlier term, as findMin (CC:159-164) returns
+ * its first argument on equality:
+ *     q = qc, b = CPU;  if !(qc <= qm): q = qm, b = MEM
+ *     for r = 0..R-1 with x_r != 0:  if !(q <= qx_r): q = qx_r, b = EXT0 + r
+ *     if q >= alloc_pods[i]: q = alloc_pods[i] - pod_count[i], b = PODS   (CC:134-136: equality fires)
+ *     if node_cap[s] > 0 and q > node_cap[s]: q = node_cap[s], b = CAP      (equality does not)
+ *     why_rows[b][cell] += 1;  why_pods[b][cell] += q (wraps);  totals[cell] += q (wraps)
+ *     left[0][cell] += fc_i - q * c            (uint64 wrap, stored as its int64 bits)
+ *     left[1][cell] += fm_i - q * m
+ *     left[2 + r][cell] += fx_r,i - q * x_r    (an unrequested resource leaves its whole fx)
+ *   fc, fm, fx are the free amounts the fit uses (0 where alloc <= used, else the wrapping
+ *   difference).  A row with no free CPU has qc = 0 and, unless a negative quotient beats it,
+ *   reason CPU.  A flagged cell (kcc_fit's divide-by-zero rule) and an empty cell have every
+ *   why_* and left entry 0; slots KCC_WHY_EXT0 + r with r >= n_ext are written 0.  With all
+ *   three outputs NULL the call launches exactly kcc_fit_capped's kernels.
+ * Argument errors and limits are kcc_fit_capped's, plus KCC_WHY_SLOTS * n_groups * n_specs <=
+ * 2^28 when a why_* output is asked for (else KCC_EINVAL).  n_nodes == 0 or n_specs == 0:
+ * KCC_OK, every output 0.  Host and async forms as kcc_fit_capped's: the async form only
+ * enqueues, allocates only when a size exceeds every earlier call's, never synchronises and
+ * reads no device value on the host (capturable into one graph on one stream).  No kernel of
+ * it waits on another workgroup: it neither sets nor reads the fault words.
+ * ------------------------------------------------------------------------- */
+#define KCC_WHY_SLOTS 8
+#define KCC_WHY_CPU 0
+#define KCC_WHY_MEM 1
+#define KCC_WHY_EXT0 2
+#define KCC_WHY_PODS 6
+#define KCC_WHY_CAP 7
+int kcc_fit_explain(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                    const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
+                    const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
+                    const int64_t* alloc_x /* [R * N] */, const int64_t* used_x /* [R * N] */,
+                    const int32_t* group /* nullable */, int64_t n_groups, int64_t n_specs,
+                    const uint64_t* spec_cpu, const int64_t* spec_mem,
+                    const int64_t* spec_x /* [R * S] */, const int64_t* node_cap /* [S], nullable */,
+                    int64_t* totals /* [G * S] */, int32_t* spec_err /* [G * S] */,
+                    int64_t* why_rows /* [8 * G * S], nullable */,
+                    int64_t* why_pods /* [8 * G * S], nullable */,
+                    int64_t* left /* [(2 + R) * G * S], nullable */);
+int kcc_fit_explain_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                          const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
+                          const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                          const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                          const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                          int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                          const int64_t* d_spec_x, const int64_t* d_node_cap, int64_t* d_totals,
+                          int32_t* d_spec_err, int64_t* d_why_rows, int64_t* d_why_pods,
+                          int64_t* d_left, void* stream);
+
+/* ---------------------------------------------------------------------------
  * A rollout plan placed on the nodes before the fit.  Every fit above answers "how many
  * replicas of one spec fit into the cluster as it stands"; its S specs are S independent
  * what-ifs.  "We roll out 40 of A and 200 of B; what fits after that, and where did they

@@ -7,10 +7,14 @@ CapacityEngine loads libkcc.so and fails loudly if it is missing.
 """
 from ._lib import KCC_EXT_MAX  # noqa: F401  (extra resources of CapacityEngine.fit_ext)
 from ._lib import KCC_DEPLOY_PACK, KCC_DEPLOY_SPREAD  # noqa: F401  (CapacityEngine.deploy)
-from .engine import (CapacityEngine, DeployResult, KccError, RequestSums,  # noqa: F401
-                     select_groups, verdict)
+from ._lib import (KCC_WHY_CAP, KCC_WHY_CPU, KCC_WHY_EXT0, KCC_WHY_MEM,  # noqa: F401
+                   KCC_WHY_PODS, KCC_WHY_SLOTS)  # (CapacityEngine.fit_explain)
+from .engine import (CapacityEngine, DeployResult, ExplainResult, KccError,  # noqa: F401
+                     RequestSums, explain_groups, select_groups, verdict)
 from .shard import node_range, shard_bounds  # noqa: F401
 
-__all__ = ["CapacityEngine", "KccError", "RequestSums", "DeployResult", "verdict",
-           "select_groups", "node_range",
-           "shard_bounds", "KCC_EXT_MAX", "KCC_DEPLOY_PACK", "KCC_DEPLOY_SPREAD"]
+__all__ = ["CapacityEngine", "KccError", "RequestSums", "DeployResult", "ExplainResult", "verdict",
+           "select_groups", "explain_groups", "node_range",
+           "shard_bounds", "KCC_EXT_MAX", "KCC_DEPLOY_PACK", "KCC_DEPLOY_SPREAD",
+           "KCC_WHY_SLOTS", "KCC_WHY_CPU", "KCC_WHY_MEM", "KCC_WHY_EXT0", "KCC_WHY_PODS",
+           "KCC_WHY_CAP"]

@@ -29,6 +29,13 @@ KCC_SPEC_OK = 0
 KCC_SPEC_DIVZERO = 1
 KCC_SPEC_FAULT = 2
 KCC_EXT_MAX = 4  # include/kcc.h: extra resources of kcc_fit_ext
+# kcc_fit_explain (include/kcc.h): the reason slots of why_rows / why_pods
+KCC_WHY_SLOTS = 8
+KCC_WHY_CPU = 0
+KCC_WHY_MEM = 1
+KCC_WHY_EXT0 = 2  # extra resource r: slot 2 + r
+KCC_WHY_PODS = 6
+KCC_WHY_CAP = 7
 # kcc_deploy (include/kcc.h): the policies; csrc/kcc_internal.h: the rows of one tile of its
 # row pass (DEPLOY_TILE) and the tile sums one pass of its scan takes (DEPLOY_SCAN_PASS)
 KCC_DEPLOY_PACK = 0
@@ -100,6 +107,10 @@ SIGNATURES = {
                              + [_vp] * 9),
     "kcc_spread_fold": (_int, [_vp, _i64, _i64] + [_vp] * 4 + [_i64] + [_vp] * 4),
     "kcc_spread_fold_async": (_int, [_vp, _i64, _i64] + [_vp] * 4 + [_i64] + [_vp] * 5),
+    "kcc_fit_explain": (_int, [_vp, _i64] + [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64, _i64]
+                        + [_vp] * 9),
+    "kcc_fit_explain_async": (_int, [_vp, _i64] + [_vp] * 6 + [_i64] + [_vp] * 3 + [_i64, _i64]
+                              + [_vp] * 10),
     "kcc_deploy": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64, _vp, _i64]
                    + [_vp] * 5 + [_int] + [_vp] * 4),
     "kcc_deploy_async": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64, _vp, _i64]

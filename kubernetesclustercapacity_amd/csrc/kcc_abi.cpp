@@ -111,6 +111,8 @@ struct Dev {
   DevBuf x_rec;                    // kcc::ExtWork::xrec (the other buffers are GrpWork's)
   DevBuf sp_qmin;                  // kcc_fit_capped: the pre-finalize minima [G S]
   DevBuf sp_cap, sp_cmin, sp_grows;  // kcc_fit_capped staging (node_cap; cell_min, group_rows)
+  DevBuf ex_free;                    // kcc_fit_explain: the groups' free amounts [(2 + R) G]
+  DevBuf ex_rows, ex_pods, ex_left;  // kcc_fit_explain staging (why_rows, why_pods, left)
   DevBuf f_cap, f_present, f_flag;   // kcc::FoldWork (kcc_spread_fold)
   DevBuf f_ct, f_ce, f_gr, f_dom, f_el, f_skew;  // kcc_spread_fold staging
   DevBuf dp_a, dp_tsum, dp_toff, dp_flag, dp_st, dp_bins;  // kcc::DeployWork (kcc_deploy)
@@ -1034,6 +1036,7 @@ void kcc_destroy(kcc_ctx* ctx) {
                       &dv.x_rec,     &dv.sp_qmin,   &dv.sp_cap,    &dv.sp_cmin,   &dv.sp_grows,
                       &dv.f_cap,     &dv.f_present, &dv.f_flag,    &dv.f_ct,      &dv.f_ce,
                       &dv.f_gr,      &dv.f_dom,     &dv.f_el,      &dv.f_skew,
+                      &dv.ex_free,   &dv.ex_rows,   &dv.ex_pods,   &dv.ex_left,
                       &dv.dp_a,      &dv.dp_tsum,   &dv.dp_toff,   &dv.dp_flag,   &dv.dp_st,
                       &dv.dp_bins,   &dv.dp_el,     &dv.dp_rep,    &dv.dp_nused,  &dv.dp_rows};
     for (DevBuf* b : bufs)
@@ -2074,6 +2077,157 @@ int kcc_fit_capped(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
                          n_ext, alloc_x, used_x, group, n_groups},
                         {n_specs, spec_cpu, spec_mem, spec_x, node_cap}, false, totals, spec_err,
                         cell_min, group_rows);
+}
+
+}  // extern "C"
+
+
+// ---- the fit explained: kcc_fit_capped with each pair's binding term kept (kcc_explain.hip) --
+
+namespace {
+
+// The three nullable plane-major outputs of kcc_fit_explain.
+struct ExplainOut {
+  int64_t* why_rows;  // [KCC_WHY_SLOTS][G S]
+  int64_t* why_pods;  // [KCC_WHY_SLOTS][G S]
+  int64_t* left;      // [2 + R][G S]
+};
+
+int check_explain(kcc_ctx* ctx, const kcc::FitNodes& nd, const kcc::FitSpecs& sp,
+                  const int64_t* totals, const int32_t* spec_err, const ExplainOut& o) {
+  const int rc = check_cells(ctx, nd, sp, false, totals, spec_err);
+  if (rc) return rc;
+  if ((o.why_rows || o.why_pods) && KCC_WHY_SLOTS * nd.G * sp.S > kcc::GRP_MAX_CELLS)
+    return fail(ctx, KCC_EINVAL, "too many cells: KCC_WHY_SLOTS x n_groups x n_specs must not exceed 2^28");
+  return KCC_OK;
+}
+
+// Device level (the caller has passed check_explain): the degenerate cases, the grid limit,
+// the workspaces and the launches on s.
+int fit_explain_dev(kcc_ctx* ctx, Dev& dv, const kcc::FitNodes& nd, const kcc::FitSpecs& sp,
+                    int64_t* totals, int32_t* spec_err, const ExplainOut& o, hipStream_t s) {
+  if (!o.why_rows && !o.why_pods && !o.left)  // kcc_fit_capped itself
+    return fit_cells_dev(ctx, dv, nd, sp, false, totals, spec_err, nullptr, nullptr, s);
+  if (sp.S == 0) return KCC_OK;  // no cells
+  const size_t cells = (size_t)(nd.G * sp.S);
+  if (nd.n == 0) {  // no rows: every cell empty
+    KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * cells, s));
+    KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * cells, s));
+    if (o.why_rows) KCC_HIP(ctx, hipMemsetAsync(o.why_rows, 0, 8 * KCC_WHY_SLOTS * cells, s));
+    if (o.why_pods) KCC_HIP(ctx, hipMemsetAsync(o.why_pods, 0, 8 * KCC_WHY_SLOTS * cells, s));
+    if (o.left) KCC_HIP(ctx, hipMemsetAsync(o.left, 0, 8 * (size_t)(2 + nd.R) * cells, s));
+    return KCC_OK;
+  }
+  if (!kcc::ext_sizes_ok(nd, sp.S))
+    return fail(ctx, KCC_EINVAL, "n_nodes x n_specs beyond one launch (2^31 - 1 workgroups of 256 x 256 pairs)");
+  if (nd.group) {
+    KCC_HIP(ctx, ensure(dv.g_count, 4 * (size_t)nd.G));
+    KCC_HIP(ctx, ensure(dv.g_cursor, 4 * (size_t)nd.G));
+    KCC_HIP(ctx, ensure(dv.g_total, 16));
+  }
+  KCC_HIP(ctx, ensure(dv.g_rec, sizeof(kcc::GrpRow) * (size_t)nd.n));
+  KCC_HIP(ctx, ensure(dv.g_rg, 4 * (size_t)nd.n));
+  KCC_HIP(ctx, ensure(dv.g_acc, 16 * cells));
+  if (nd.R > 0) KCC_HIP(ctx, ensure(dv.x_rec, sizeof(kcc::ExtCol) * (size_t)nd.n * (size_t)nd.R));
+  if (o.left) KCC_HIP(ctx, ensure(dv.ex_free, 8 * (size_t)(2 + nd.R) * (size_t)nd.G));
+  const kcc::ExtWork w{{as<uint32_t>(dv.g_count), as<uint32_t>(dv.g_cursor), as<uint32_t>(dv.g_total),
+                        as<kcc::GrpRow>(dv.g_rec), as<int32_t>(dv.g_rg), as<int64_t>(dv.g_acc)},
+                       as<kcc::ExtCol>(dv.x_rec)};
+  KCC_HIP(ctx, kcc::launch_fit_explain(nd, sp, w, as<unsigned long long>(dv.ex_free), totals,
+                                       spec_err, o.why_rows, o.why_pods, o.left, s));
+  return KCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kcc_fit_explain_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                          const int64_t* d_alloc_mem, const int64_t* d_alloc_pods,
+                          const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                          const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                          const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                          int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                          const int64_t* d_spec_x, const int64_t* d_node_cap, int64_t* d_totals,
+                          int32_t* d_spec_err, int64_t* d_why_rows, int64_t* d_why_pods,
+                          int64_t* d_left, void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  const kcc::FitNodes nd{n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count, d_used_cpu,
+                         d_used_mem, n_ext, d_alloc_x, d_used_x, d_group, n_groups};
+  const kcc::FitSpecs sp{n_specs, d_spec_cpu, d_spec_mem, d_spec_x, d_node_cap};
+  const ExplainOut o{d_why_rows, d_why_pods, d_left};
+  const int rc = check_explain(ctx, nd, sp, d_totals, d_spec_err, o);
+  if (rc) return rc;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  return fit_explain_dev(ctx, dv, nd, sp, d_totals, d_spec_err, o, static_cast<hipStream_t>(stream));
+}
+
+int kcc_fit_explain(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                    const int64_t* alloc_mem, const int64_t* alloc_pods, const int64_t* pod_count,
+                    const uint64_t* used_cpu, const int64_t* used_mem, int64_t n_ext,
+                    const int64_t* alloc_x, const int64_t* used_x, const int32_t* group,
+                    int64_t n_groups, int64_t n_specs, const uint64_t* spec_cpu,
+                    const int64_t* spec_mem, const int64_t* spec_x, const int64_t* node_cap,
+                    int64_t* totals, int32_t* spec_err, int64_t* why_rows, int64_t* why_pods,
+                    int64_t* left) {
+  if (!ctx) return KCC_EINVAL;
+  kcc::FitNodes nd{n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                   n_ext, alloc_x, used_x, group, n_groups};
+  kcc::FitSpecs sp{n_specs, spec_cpu, spec_mem, spec_x, node_cap};
+  const ExplainOut o{why_rows, why_pods, left};
+  int rc = check_explain(ctx, nd, sp, totals, spec_err, o);
+  if (rc) return rc;
+  if (!why_rows && !why_pods && !left)  // kcc_fit_capped itself
+    return fit_cells_host(ctx, nd, sp, false, totals, spec_err, nullptr, nullptr);
+  const int64_t n = n_nodes, S = n_specs;
+  if (S == 0) return KCC_OK;
+  const size_t cells = (size_t)(n_groups * S);
+  const size_t why_bytes = 8 * (size_t)KCC_WHY_SLOTS * cells, left_bytes = 8 * (size_t)(2 + n_ext) * cells;
+  if (n == 0) {
+    memset(totals, 0, 8 * cells);
+    memset(spec_err, 0, 4 * cells);
+    if (why_rows) memset(why_rows, 0, why_bytes);
+    if (why_pods) memset(why_pods, 0, why_bytes);
+    if (left) memset(left, 0, left_bytes);
+    return KCC_OK;
+  }
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  if ((rc = stage(ctx, dv, dv.alloc_cpu, nd.alloc_cpu, n)) ||
+      (rc = stage(ctx, dv, dv.alloc_mem, nd.alloc_mem, n)) ||
+      (rc = stage(ctx, dv, dv.alloc_pods, nd.alloc_pods, n)) ||
+      (rc = stage(ctx, dv, dv.pod_count, nd.pod_count, n)) ||
+      (rc = stage(ctx, dv, dv.used_cpu, nd.used_cpu, n)) ||
+      (rc = stage(ctx, dv, dv.used_mem, nd.used_mem, n)) ||
+      (rc = stage(ctx, dv, dv.x_alloc, nd.alloc_x, nd.R * n)) ||
+      (rc = stage(ctx, dv, dv.x_used, nd.used_x, nd.R * n)) ||
+      (rc = stage(ctx, dv, dv.g_group, nd.group, n)) ||
+      (rc = stage(ctx, dv, dv.spec_cpu, sp.spec_cpu, S)) ||
+      (rc = stage(ctx, dv, dv.spec_mem, sp.spec_mem, S)) ||
+      (rc = stage(ctx, dv, dv.x_spec, sp.spec_x, nd.R * S)) ||
+      (rc = stage(ctx, dv, dv.sp_cap, sp.node_cap, S)))
+    return rc;
+  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
+  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
+  if (why_rows) KCC_HIP(ctx, ensure(dv.ex_rows, why_bytes));
+  if (why_pods) KCC_HIP(ctx, ensure(dv.ex_pods, why_bytes));
+  if (left) KCC_HIP(ctx, ensure(dv.ex_left, left_bytes));
+  const ExplainOut d{why_rows ? as<int64_t>(dv.ex_rows) : nullptr,
+                     why_pods ? as<int64_t>(dv.ex_pods) : nullptr,
+                     left ? as<int64_t>(dv.ex_left) : nullptr};
+  rc = fit_explain_dev(ctx, dv, nd, sp, as<int64_t>(dv.totals), as<int32_t>(dv.err), d, dv.stream);
+  if (rc) return rc;
+  KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
+  KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
+  if (why_rows)
+    KCC_HIP(ctx, hipMemcpyAsync(why_rows, dv.ex_rows.p, why_bytes, hipMemcpyDeviceToHost, dv.stream));
+  if (why_pods)
+    KCC_HIP(ctx, hipMemcpyAsync(why_pods, dv.ex_pods.p, why_bytes, hipMemcpyDeviceToHost, dv.stream));
+  if (left)
+    KCC_HIP(ctx, hipMemcpyAsync(left, dv.ex_left.p, left_bytes, hipMemcpyDeviceToHost, dv.stream));
+  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
+  return KCC_OK;
 }
 
 }  // extern "C"

@@ -573,8 +573,8 @@ hipError_t launch_fit_rows(int64_t n, const uint64_t* alloc_cpu, const int64_t* 
 // ---- the cell fits: per node-group x spec totals -------------
 // kcc_fit_grouped, kcc_fit_ext and kcc_fit_capped are one path: the records (kcc_ext.hip:
 // ext_rows<R>, or kcc_groups.hip's hist / scan and ext_scatter<R> with group ids), one pair
-// loop (ext_pairs_body below, as ext_pairs<R> or kcc_spread.hip's cap_pairs<R>) and a
-// finalize.  The grouped fit is the R = 0 instance with group ids.
+// loop (ext_pairs_body below, as ext_pairs<R>, kcc_spread.hip's cap_pairs<R> or
+// kcc_explain.hip's why_pairs<R>) and a finalize.  The grouped fit is the R = 0 instance with group ids.
 //
 // The record of one node row, placed in group order: the exact path's integers (fc / fm
 // are 0 where the reference's `alloc <= used` branch divides nothing) and, for a fast row
@@ -720,14 +720,44 @@ constexpr unsigned long long SPREAD_SIGN = 1ull << 63;  // qmin[] cells: q ^ SPR
 // selects), and flushes the minimum with a 64-bit atomic min where grp_flush runs; without
 // SPREAD none of that code exists.  total == nullptr: the n_rec records of the ungrouped
 // pass; else *total (the rows with a valid group id, from grp_scan).
-template <int R, bool SPREAD>
+// WHY (kcc_explain.hip's why_pairs<R>, with SPREAD) carries the term that won
+// each pair's findMin along: b in [0, R + 4) — CPU, memory, extra resource r at 2 + r, then
+// the pod-slot clamp and the cap — under findMin's tie rule (the earlier term keeps an equal
+// quotient; the clamp fires on equality, the cap does not).  Per lane R + 4 row counters and
+// R + 4 sums of q, indexed statically, flushed where grp_flush runs into the plane-major
+// why_rows / why_pods [KCC_WHY_SLOTS][cells] (either may be nullptr); without WHY none of
+// that code exists.
+constexpr int WHY_SLOTS = 8;  // include/kcc.h KCC_WHY_SLOTS
+constexpr int WHY_PODS = 6, WHY_CAP = 7;
+static_assert(2 + EXT_MAX <= WHY_PODS, "the extra resources' slots end below KCC_WHY_PODS");
+
+template <int R>
+__device__ inline void why_flush(unsigned long long* __restrict__ why_rows,
+                                 unsigned long long* __restrict__ why_pods, int64_t cells,
+                                 int64_t cell, bool live, uint32_t (&wr)[R + 4],
+                                 uint64_t (&wp)[R + 4]) {
+#pragma unroll
+  for (int k = 0; k < R + 4; ++k) {
+    const int64_t slot = k < R + 2 ? k : WHY_PODS + (k - (R + 2));
+    if (live && wr[k] != 0) {  // (no rows: the sum is 0 too)
+      if (why_rows) atomicAdd(why_rows + slot * cells + cell, (unsigned long long)wr[k]);
+      if (why_pods) atomicAdd(why_pods + slot * cells + cell, (unsigned long long)wp[k]);
+    }
+    wr[k] = 0;
+    wp[k] = 0;
+  }
+}
+
+template <int R, bool SPREAD, bool WHY = false>
 __device__ inline void ext_pairs_body(
     const uint32_t* __restrict__ total, int64_t n_rec, int64_t S, int64_t sblocks,
     const uint64_t* __restrict__ spec_cpu, const int64_t* __restrict__ spec_mem,
     const int64_t* __restrict__ spec_x, const GrpRow* __restrict__ rec,
     const ExtCol* __restrict__ xrec, const int32_t* __restrict__ rg, int64_t* __restrict__ acc,
     unsigned long long* __restrict__ cnt, const int64_t* __restrict__ node_cap,
-    unsigned long long* __restrict__ qmin) {
+    unsigned long long* __restrict__ qmin, unsigned long long* __restrict__ why_rows = nullptr,
+    unsigned long long* __restrict__ why_pods = nullptr, int64_t cells = 0) {
+  static_assert(!WHY || SPREAD, "WHY is built on the capped loop");
   constexpr int RR = R ? R : 1;
   __shared__ GrpRow s_rec[GRP_RUN];
   __shared__ ExtCol s_x[GRP_RUN * RR];
@@ -773,6 +803,15 @@ __device__ inline void ext_pairs_body(
   int64_t sum = 0;
   [[maybe_unused]] int64_t mn = INT64_MAX;
   unsigned long long z = 0;
+  [[maybe_unused]] uint32_t wr[R + 4];
+  [[maybe_unused]] uint64_t wp[R + 4];
+  if constexpr (WHY) {
+#pragma unroll
+    for (int k = 0; k < R + 4; ++k) {
+      wr[k] = 0;
+      wp[k] = 0;
+    }
+  }
   int gcur = __builtin_amdgcn_readfirstlane(s_rg[0]) & (GRP_ROW_FAST - 1);
   for (int j = 0; j < nr; ++j) {
     const int meta = __builtin_amdgcn_readfirstlane(s_rg[j]);
@@ -783,19 +822,23 @@ __device__ inline void ext_pairs_body(
         if (qmin && live) atomicMin(qmin + (int64_t)gcur * S + s, (unsigned long long)mn ^ SPREAD_SIGN);
         mn = INT64_MAX;
       }
+      if constexpr (WHY) why_flush<R>(why_rows, why_pods, cells, (int64_t)gcur * S + s, live, wr, wp);
       sum = 0;
       z = 0;
       gcur = g;
     }
     const GrpRow r = s_rec[j];
     int64_t q;
+    [[maybe_unused]] int b = 0;  // WHY: the term that holds q (the selects below are findMin's tie rule)
     if (wave_fast && (meta & GRP_ROW_FAST)) {  // wave-uniform
       const double tc = grp_div(r.fcd, cd, rc);
       const double tm = grp_div(r.fmd, md, rm);
       double t = tc <= tm ? tc : tm;  // findMin (CC:133)
+      if constexpr (WHY) b = tc <= tm ? 0 : 1;
 #pragma unroll
       for (int k = 0; k < R; ++k) {
         const double tx = grp_div(s_x[j * RR + k].fxd, xd[k], rx[k]);
+        if constexpr (WHY) b = (x[k] != 0 && tx < t) ? 2 + k : b;
         t = (x[k] != 0 && tx < t) ? tx : t;  // the unrequested lane's quotient is never used
       }
       q = (int64_t)(int32_t)t;  // <= free CPU < 2^31
@@ -812,28 +855,40 @@ __device__ inline void ext_pairs_body(
         else qm = r.fm / m;
       }
       q = qc <= qm ? qc : qm;  // findMin, CC:133
+      if constexpr (WHY) b = qc <= qm ? 0 : 1;
 #pragma unroll
       for (int k = 0; k < R; ++k) {
         const int64_t fx = s_x[j * RR + k].fx;
         if (x[k] != 0) {  // zero: not requested
           int64_t qx = 0;
           if (fx != 0) qx = x[k] == -1 ? (int64_t)(0ull - (uint64_t)fx) : fx / x[k];
+          if constexpr (WHY) b = q <= qx ? b : 2 + k;
           q = q <= qx ? q : qx;
         }
       }
       z += dz ? 1u : 0u;
     }
+    if constexpr (WHY) b = q >= r.P ? R + 2 : b;
     if (q >= r.P) q = r.cl;  // CC:134-136, after all the mins
     if constexpr (SPREAD) {
       mn = q < mn ? q : mn;      // the cell's minimum: before the cap
+      if constexpr (WHY) b = q > capv ? R + 3 : b;
       q = q > capv ? capv : q;   // at most node_cap[s] on one node: after the clamp
     }
     sum = (int64_t)((uint64_t)sum + (uint64_t)q);
+    if constexpr (WHY) {
+#pragma unroll
+      for (int k = 0; k < R + 4; ++k) {  // static indices: the arrays stay in registers
+        wr[k] += b == k ? 1u : 0u;
+        wp[k] += b == k ? (uint64_t)q : 0ull;
+      }
+    }
   }
   grp_flush(acc, cnt, (int64_t)gcur * S + s, live, sum, z);
   if constexpr (SPREAD) {
     if (qmin && live) atomicMin(qmin + (int64_t)gcur * S + s, (unsigned long long)mn ^ SPREAD_SIGN);
   }
+  if constexpr (WHY) why_flush<R>(why_rows, why_pods, cells, (int64_t)gcur * S + s, live, wr, wp);
 }
 
 // The pair loop's launch: kernel is ext_pairs_kernel<R>, or cap_pairs_kernel<R> with its two
@@ -873,6 +928,18 @@ hipError_t launch_spread_fold(int64_t G, int64_t S, const int64_t* cell_totals,
                               const int32_t* domain_of, int64_t D, const uint8_t* eligible,
                               const int64_t* max_skew, const FoldWork& w, int64_t* totals,
                               int32_t* spec_err, hipStream_t s);
+
+// ---- the fit explained (kcc_explain.hip) ---------------------------
+// kcc_fit_explain: launch_fit_capped's totals / spec_err and three nullable plane-major
+// outputs: why_rows / why_pods [WHY_SLOTS][G S] (rows and replicas of each cell by the term
+// that holds the row's q) and left [2 + R][G S] (what stays free: per group the free amounts
+// summed, less request x total).  free: [(2 + R) G] workspace of left.  All three nullptr:
+// the launches of launch_fit_capped themselves.  why_rows / why_pods are zeroed here and
+// accumulated into directly; the finalize zeroes the flagged cells.
+constexpr int WHY_FREE_IPL = 16;  // records per lane of why_free (a wave: 64 x 16, lane-strided)
+hipError_t launch_fit_explain(const FitNodes& nd, const FitSpecs& sp, const ExtWork& w,
+                              unsigned long long* free, int64_t* totals, int32_t* spec_err,
+                              int64_t* why_rows, int64_t* why_pods, int64_t* left, hipStream_t s);
 
 // ---- a rollout plan committed to the node rows (kcc_deploy.hip) ------
 // Rows in tiles of DEPLOY_TILE: 256 threads x DEPLOY_IPT consecutive rows (kcc_deploy.hip).

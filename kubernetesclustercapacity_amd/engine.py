@@ -73,6 +73,18 @@ class DeployResult:
     rows: np.ndarray | None
 
 
+@dataclass
+class ExplainResult:
+    """What CapacityEngine.fit_explain returns: fit_capped's totals / err, the rows and the
+    replicas of each cell by reason ([KCC_WHY_SLOTS, G, S]) and what stays free ([2 + R, G, S]);
+    without group ids the G axis is dropped.  A field not asked for is None."""
+    totals: np.ndarray
+    err: np.ndarray
+    why_rows: np.ndarray | None
+    why_pods: np.ndarray | None
+    left: np.ndarray | None
+
+
 class CapacityEngine:
     """One libkcc context (one device, or n_gpus devices with node sharding + RCCL)."""
 
@@ -385,6 +397,57 @@ class CapacityEngine:
                                              group, G, cap2, want_min=False)
         return self.spread_fold(t.reshape(G, S), e.reshape(G, S), grows, zone_of, n_zones,
                                 eligible, max_skew)
+
+    # -- the fit explained (opt-in; include/kcc.h) ----------------------
+    def fit_explain(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                    alloc_x, used_x, spec_cpu, spec_mem, spec_x, group=None, n_groups=1,
+                    node_cap=None, want_rows=True, want_pods=True, want_left=True
+                    ) -> "ExplainResult":
+        """fit_capped with the term that binds each node kept: per cell the rows (why_rows) and
+        the replicas (why_pods) by reason — slot KCC_WHY_CPU, KCC_WHY_MEM, KCC_WHY_EXT0 + r,
+        KCC_WHY_PODS (the pod-slot clamp), KCC_WHY_CAP (node_cap); ties keep the earlier term —
+        and what stays free once the cell holds its total (left: plane 0 CPU, 1 memory, 2 + r
+        extra resource r).  Opt-in, not the reference's arithmetic; totals / err are
+        fit_capped's bit for bit.  A flagged or empty cell has every entry 0.  want_* False:
+        that field is None (all three False: fit_capped's own kernels).  alloc_x / used_x /
+        spec_x may be None (no extra resource)."""
+        a, R, ax, ux, group, G, sc, sm, sx, totals, err = self._cell_args(
+            (alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem), spec_cpu, spec_mem,
+            group, n_groups, alloc_x, used_x, spec_x)
+        S = sc.size
+        cap = None if node_cap is None else _arr(node_cap, np.int64)
+        if cap is not None and cap.shape != (S,):
+            raise ValueError("node_cap must be [S]")
+        g0 = max(G, 0)
+        wr = np.zeros((_lib.KCC_WHY_SLOTS, g0, S), np.int64) if want_rows else None
+        wp = np.zeros((_lib.KCC_WHY_SLOTS, g0, S), np.int64) if want_pods else None
+        left = np.zeros((2 + R, g0, S), np.int64) if want_left else None
+        self._check(self._lib.kcc_fit_explain(self._h, a[0].size, *[_p(x) for x in a], R, _p(ax),
+                                              _p(ux), _p(group), G, S, _p(sc), _p(sm), _p(sx),
+                                              _p(cap), _p(totals), _p(err), _p(wr), _p(wp),
+                                              _p(left)))
+        if group is None:
+            def drop(v, axis):
+                return None if v is None else v.take(0, axis=axis)
+            return ExplainResult(totals[0], err[0], drop(wr, 1), drop(wp, 1), drop(left, 1))
+        return ExplainResult(totals, err, wr, wp, left)
+
+    def fit_explain_async(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                          n_ext, alloc_x, used_x, group, n_groups, spec_cpu, spec_mem, spec_x,
+                          node_cap, totals, spec_err, why_rows=None, why_pods=None, left=None,
+                          stream=None):
+        """Device form of fit_explain (torch tensors on the engine's device, as
+        fit_capped_async's; why_rows / why_pods int64 of KCC_WHY_SLOTS * n_groups * S elements,
+        left of (2 + n_ext) * n_groups * S, plane-major).  The arguments go to the C-ABI as
+        they are (None: NULL), which validates them."""
+        n = 0 if alloc_cpu is None else alloc_cpu.numel()
+        s = 0 if spec_cpu is None else spec_cpu.numel()
+        self._check(self._lib.kcc_fit_explain_async(
+            self._h, n, _dp(alloc_cpu), _dp(alloc_mem), _dp(alloc_pods), _dp(pod_count),
+            _dp(used_cpu), _dp(used_mem), int(n_ext), _dp(alloc_x), _dp(used_x), _dp(group),
+            int(n_groups), s, _dp(spec_cpu), _dp(spec_mem), _dp(spec_x), _dp(node_cap),
+            _dp(totals), _dp(spec_err), _dp(why_rows), _dp(why_pods), _dp(left),
+            _stream(stream)))
 
     # -- a rollout plan placed on the nodes (opt-in; include/kcc.h, DESIGN.md §4.12) ----
     def deploy(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
@@ -865,6 +928,40 @@ def select_groups(totals, err, eligible):
     s = np.where(m, t, 0).astype(np.int64).view(np.uint64).sum(axis=0, dtype=np.uint64)
     out = np.where(flagged, np.uint64(0), s).astype(np.uint64).view(np.int64)
     return out, flagged.astype(np.int32)
+
+
+def explain_groups(res, eligible, group_rows=None):
+    """fit_explain's cells folded over the eligible live groups, per plane (host arithmetic on
+    G x S numbers, like select_groups, whose flag rule it uses).  res: a grouped ExplainResult;
+    eligible: bool [G, S] or [G]; group_rows int64 [G] (None: every group is live; else the
+    groups with no row are left out — their cells cannot flag a spec).  Returns an
+    ExplainResult without the G axis: totals / err as select_groups gives them, every plane
+    the wrapping sum of its eligible live cells, 0 where err[s] is set."""
+    t = np.asarray(res.totals, np.int64)
+    if t.ndim != 2:
+        raise ValueError("res must hold [G, S] cells")
+    m = np.asarray(eligible, bool)
+    if m.shape == t.shape[:1]:
+        m = np.broadcast_to(m[:, None], t.shape)
+    if m.shape != t.shape:
+        raise ValueError("eligible must be [G, S] or [G]")
+    if group_rows is not None:
+        gr = np.asarray(group_rows, np.int64)
+        if gr.shape != t.shape[:1]:
+            raise ValueError("group_rows must be [G]")
+        m = m & (gr > 0)[:, None]
+    totals, err = select_groups(t, res.err, m)
+
+    def fold(planes):
+        if planes is None:
+            return None
+        p = np.asarray(planes, np.int64)
+        if p.ndim != 3 or p.shape[1:] != t.shape:
+            raise ValueError("planes must be [K, G, S]")
+        s = np.where(m[None], p, 0).astype(np.int64).view(np.uint64).sum(axis=1, dtype=np.uint64)
+        return np.where((err != 0)[None], np.uint64(0), s).astype(np.uint64).view(np.int64)
+
+    return ExplainResult(totals, err, fold(res.why_rows), fold(res.why_pods), fold(res.left))
 
 
 def verdict(totals, replicas):
