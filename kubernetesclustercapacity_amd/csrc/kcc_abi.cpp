@@ -17,17 +17,40 @@
 
 namespace {
 
+// A device allocation and its owner: move-only, freed with the object (the context's
+// teardown has synchronised the streams by then).  It only ever grows (ensure).
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) {
+    o.p = nullptr;
+    o.bytes = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      bytes = o.bytes;
+      o.p = nullptr;
+      o.bytes = 0;
+    }
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
 };
 
 hipError_t ensure(DevBuf& b, size_t bytes) {
   if (bytes == 0) bytes = 16;
   if (b.bytes >= bytes) return hipSuccess;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
+  b.release();
   hipError_t e = hipMalloc(&b.p, bytes);
   if (e == hipSuccess) b.bytes = bytes;
   return e;
@@ -40,9 +63,7 @@ hipError_t ensure(DevBuf& b, size_t bytes) {
 hipError_t ensure_uncached(DevBuf& b, size_t bytes) {
   if (bytes == 0) bytes = 16;
   if (b.bytes >= bytes) return hipSuccess;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
+  b.release();
   hipError_t e = hipExtMallocWithFlags(&b.p, bytes, hipDeviceMallocUncached);
   if (e == hipSuccess) b.bytes = bytes;
   return e;
@@ -100,28 +121,19 @@ struct Dev {
   DevBuf fast_cl;          // the clamp in the fit: each streamed row's clamp value
   int stream_chunks = 0;   // node chunks of the last fit prepare (their stream counters)
   int64_t prep_nodes = -1, prep_specs = -1;  // sizes the workspace was last prepared for
-  // staging of the host-array entry points
-  DevBuf ptr, cpu, mem, cpul, meml, used_cpu, used_mem, lim_cpu, lim_mem;
-  DevBuf alloc_cpu, alloc_mem, alloc_pods, pod_count, spec_cpu, spec_mem, partial, totals, err;
-  DevBuf p_bytes, p_off, p_out, p_st;  // kcc_parse_* staging
-  DevBuf k_key;                        // kcc_*_keyed staging
-  DevBuf g_group;                                       // kcc_fit_grouped staging (group ids)
+  // staging of the host-array entry points (Stage): the k-th array a call stages takes slot
+  // k; the slots only grow, and a synchronous call has let go of them when it returns
+  std::vector<DevBuf> slots;
+  DevBuf partial;                                         // the fit's per-spec partials [2 S] per shard
   DevBuf g_count, g_cursor, g_total, g_rec, g_rg, g_acc;  // kcc::GrpWork (grouped fit)
-  DevBuf x_alloc, x_used, x_spec;  // kcc_fit_ext staging (the extra columns)
   DevBuf x_rec;                    // kcc::ExtWork::xrec (the other buffers are GrpWork's)
   DevBuf sp_qmin;                  // kcc_fit_capped: the pre-finalize minima [G S]
-  DevBuf sp_cap, sp_cmin, sp_grows;  // kcc_fit_capped staging (node_cap; cell_min, group_rows)
-  DevBuf ex_free;                    // kcc_fit_explain: the groups' free amounts [(2 + R) G]
-  DevBuf ex_rows, ex_pods, ex_left;  // kcc_fit_explain staging (why_rows, why_pods, left)
+  DevBuf ex_free;                  // kcc_fit_explain: the groups' free amounts [(2 + R) G]
   DevBuf f_cap, f_present, f_flag;   // kcc::FoldWork (kcc_spread_fold)
-  DevBuf f_ct, f_ce, f_gr, f_dom, f_el, f_skew;  // kcc_spread_fold staging
   DevBuf dp_a, dp_tsum, dp_toff, dp_flag, dp_st, dp_bins;  // kcc::DeployWork (kcc_deploy)
-  DevBuf dp_el, dp_rep, dp_nused, dp_rows;  // kcc_deploy staging (eligible, replicas; outputs)
   DevBuf kb_counts, kb_tot, kb_sr, kb_sv;  // kcc::KeyedWork (bucketed keyed reduce)
   DevBuf kb_part, kb_arrive;               // one-sweep gather: part rows, arrivals (zeroed)
   DevBuf kb_esc_n, kb_esc_row, kb_esc_cpu, kb_esc_mem;
-  // kcc_pod_requests / kcc_reduce_requests_pods staging (app containers in cpu / mem)
-  DevBuf q_ptr, q_iptr, q_icpu, q_imem, q_rst, q_ocpu, q_omem, q_pcpu, q_pmem;
   // one-shot exchange over xGMI peer memory (kcc_p2p_*): this rank's mailbox (exported),
   // the push arrival counter (u32 word 0) and the last pushed epoch (u64 word 1, advanced
   // by the kernel); the peers' mapped mailboxes
@@ -198,6 +210,10 @@ int check_csr(kcc_ctx* ctx, int64_t n_nodes, int64_t n_cont, const int64_t* ptr)
   return KCC_OK;
 }
 
+// Entries of a CSR offset array that are read: none without rows (check_csr asks for no
+// array then).
+int64_t csr_len(int64_t n) { return n > 0 ? n + 1 : 0; }
+
 // Contiguous node ranges, balanced by node count (the fit dominates).
 void shard_nodes(int64_t n_nodes, int n, std::vector<int64_t>& lo, std::vector<int64_t>& hi) {
   lo.resize(n);
@@ -206,15 +222,6 @@ void shard_nodes(int64_t n_nodes, int n, std::vector<int64_t>& lo, std::vector<i
     lo[d] = n_nodes * d / n;
     hi[d] = n_nodes * (d + 1) / n;
   }
-}
-
-template <class T>
-int h2d(kcc_ctx* ctx, Dev& dv, DevBuf& buf, const T* src, int64_t count) {
-  KCC_HIP(ctx, ensure(buf, sizeof(T) * (size_t)(count > 0 ? count : 1)));
-  if (count > 0)
-    KCC_HIP(ctx, hipMemcpyAsync(buf.p, src, sizeof(T) * (size_t)count, hipMemcpyHostToDevice,
-                                dv.stream));
-  return KCC_OK;
 }
 
 // ---- device-level pipeline pieces (no host sync, no allocation beyond growth) ----
@@ -263,23 +270,110 @@ int check_faults(kcc_ctx* ctx) {
                   "KCC_SPEC_FAULT) until kcc_clear_faults");
 }
 
-int reduce_async_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, int64_t n_cont, const int64_t* ptr,
-                     const uint64_t* cpu, const int64_t* mem, const uint64_t* cpul,
-                     const int64_t* meml, uint64_t* used_cpu, int64_t* used_mem,
-                     uint64_t* lim_cpu, int64_t* lim_mem, hipStream_t s) {
+// One host-array call's staging on dv.stream.  The k-th array the call stages takes
+// dv.slots[k].  Every operation takes a nullable host pointer and a count, and leaves the
+// pointer naming the device copy: NULL stays NULL, a count of 0 copies nothing.
+class Stage {
+ public:
+  Stage(kcc_ctx* ctx, Dev& dv) : ctx_(ctx), dv_(dv) {}
+
+  template <class T>
+  int in(const T*& p, int64_t count) {  // an input: copied to its slot
+    if (!p) return KCC_OK;
+    const size_t bytes = size_of<T>(count);
+    void* d = nullptr;
+    const int rc = slot(bytes, &d);
+    if (rc) return rc;
+    if (bytes) KCC_HIP(ctx_, hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, dv_.stream));
+    p = static_cast<const T*>(d);
+    return KCC_OK;
+  }
+  template <class T>
+  int out(T*& p, int64_t count) {  // an output: finish() copies its slot back
+    if (!p) return KCC_OK;
+    T* const host = p;
+    const int rc = tmp(p, count);
+    if (!rc && count > 0) back_.push_back({host, p, size_of<T>(count)});
+    return rc;
+  }
+  template <class T>
+  int inout(T*& p, int64_t count) {  // state the call updates in place: both of the above
+    T* const host = p;
+    const T* d = p;
+    const int rc = in(d, count);
+    if (!rc && host && count > 0) back_.push_back({host, d, size_of<T>(count)});
+    p = const_cast<T*>(d);
+    return rc;
+  }
+  template <class T>
+  int tmp(T*& p, int64_t count) {  // device only: one launch's output, the next one's input
+    void* d = nullptr;
+    const int rc = slot(size_of<T>(count), &d);
+    p = static_cast<T*>(d);
+    return rc;
+  }
+  // Back to slot 0 (run_host, per node shard: a device's shards reuse the same slots, in
+  // stream order).
+  void rewind() { next_ = 0; }
+  // Every output back to the host, then the call's one synchronisation.
+  int finish(bool faults = false) {
+    for (const Back& b : back_)
+      KCC_HIP(ctx_, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, dv_.stream));
+    back_.clear();
+    KCC_HIP(ctx_, hipStreamSynchronize(dv_.stream));
+    return faults ? check_faults(ctx_) : KCC_OK;
+  }
+
+ private:
+  struct Back {
+    void* host;
+    const void* dev;
+    size_t bytes;
+  };
+  template <class T>
+  static size_t size_of(int64_t count) {
+    return sizeof(T) * (size_t)(count > 0 ? count : 0);
+  }
+  int slot(size_t bytes, void** d) {
+    if (next_ == dv_.slots.size()) dv_.slots.emplace_back();
+    DevBuf& b = dv_.slots[next_++];
+    KCC_HIP(ctx_, ensure(b, bytes));
+    *d = b.p;
+    return KCC_OK;
+  }
+  kcc_ctx* ctx_;
+  Dev& dv_;
+  size_t next_ = 0;
+  std::vector<Back> back_;
+};
+
+// Argument checks of the reduce's two entry points (host or device pointers alike).
+int check_reduce(kcc_ctx* ctx, int64_t n_nodes, int64_t n_cont, const int64_t* ptr,
+                 const uint64_t* cpu, const int64_t* mem, const uint64_t* cpul,
+                 const int64_t* meml, const uint64_t* used_cpu, const int64_t* used_mem,
+                 const uint64_t* lim_cpu, const int64_t* lim_mem) {
   if (n_nodes < 0 || n_cont < 0) return fail(ctx, KCC_EINVAL, "negative size");
   if (n_nodes == 0) return n_cont == 0 ? KCC_OK : fail(ctx, KCC_EINVAL, "containers without nodes");
   if (n_nodes >= kcc::RED_MAX_NODES)
     return fail(ctx, KCC_EINVAL, "too many nodes per device (max 2^28 - 1)");
   if (!ptr || !used_cpu || !used_mem) return fail(ctx, KCC_EINVAL, "NULL node_ptr/output");
   if (n_cont > 0 && (!cpu || !mem)) return fail(ctx, KCC_EINVAL, "NULL cpu_req/mem_req");
-  const bool lim = cpul != nullptr || meml != nullptr;
-  if (lim && (!cpul || !meml || !lim_cpu || !lim_mem))
+  if ((cpul || meml) && (!cpul || !meml || !lim_cpu || !lim_mem))
     return fail(ctx, KCC_EINVAL, "limits need cpu_lim, mem_lim, lim_cpu and lim_mem");
+  return KCC_OK;
+}
+
+int reduce_async_dev(kcc_ctx* ctx, Dev& dv, int64_t n_nodes, int64_t n_cont, const int64_t* ptr,
+                     const uint64_t* cpu, const int64_t* mem, const uint64_t* cpul,
+                     const int64_t* meml, uint64_t* used_cpu, int64_t* used_mem,
+                     uint64_t* lim_cpu, int64_t* lim_mem, hipStream_t s) {
+  int rc = check_reduce(ctx, n_nodes, n_cont, ptr, cpu, mem, cpul, meml, used_cpu, used_mem,
+                        lim_cpu, lim_mem);
+  if (rc || n_nodes == 0) return rc;
+  const bool lim = cpul != nullptr;
   if (!aligned16(cpu) || !aligned16(mem) || (lim && (!aligned16(cpul) || !aligned16(meml))))
     return fail(ctx, KCC_EINVAL, "container arrays must be 16-byte aligned");
-  int rc = reduce_ws(ctx, dv, s);
-  if (rc) return rc;
+  if ((rc = reduce_ws(ctx, dv, s))) return rc;
   KCC_HIP(ctx, kcc::launch_reduce(n_nodes, 0, n_cont, ptr, cpu, mem, lim ? cpul : nullptr,
                                   lim ? meml : nullptr, used_cpu, used_mem, lim ? lim_cpu : nullptr,
                                   lim ? lim_mem : nullptr, as<uint64_t>(dv.red_tail),
@@ -781,43 +875,50 @@ int run_host(kcc_ctx* ctx, bool with_reduce, int64_t n_nodes, int64_t n_cont,
     KCC_HIP(ctx, hipSetDevice(dv.device));
     KCC_HIP(ctx, ensure(dv.partial, sizeof(int64_t) * 2 * (size_t)n_specs * (size_t)slots));
   }
+  std::vector<Stage> stages;  // one per device, rewound per shard
+  stages.reserve(nd);
+  for (Dev& dv : ctx->devs) stages.emplace_back(ctx, dv);
   for (int sh = 0; sh < ns; ++sh) {
     Dev& dv = ctx->devs[sh % nd];
+    Stage& st = stages[sh % nd];
+    st.rewind();
     int64_t* part = as<int64_t>(dv.partial) + (size_t)(sh / nd) * 2 * (size_t)n_specs;
     KCC_HIP(ctx, hipSetDevice(dv.device));
     const int64_t n = hi[sh] - lo[sh];
+    const uint64_t *a_cpu = alloc_cpu + lo[sh], *s_cpu = spec_cpu;
+    const int64_t *a_mem = alloc_mem + lo[sh], *a_pods = alloc_pods + lo[sh];
+    const int64_t *pods = pod_count + lo[sh], *s_mem = spec_mem;
     int rc;
-    if ((rc = h2d(ctx, dv, dv.alloc_cpu, alloc_cpu + lo[sh], n))) return rc;
-    if ((rc = h2d(ctx, dv, dv.alloc_mem, alloc_mem + lo[sh], n))) return rc;
-    if ((rc = h2d(ctx, dv, dv.alloc_pods, alloc_pods + lo[sh], n))) return rc;
-    if ((rc = h2d(ctx, dv, dv.pod_count, pod_count + lo[sh], n))) return rc;
-    if ((rc = h2d(ctx, dv, dv.spec_cpu, spec_cpu, n_specs))) return rc;
-    if ((rc = h2d(ctx, dv, dv.spec_mem, spec_mem, n_specs))) return rc;
+    if ((rc = st.in(a_cpu, n)) || (rc = st.in(a_mem, n)) || (rc = st.in(a_pods, n)) ||
+        (rc = st.in(pods, n)) || (rc = st.in(s_cpu, n_specs)) || (rc = st.in(s_mem, n_specs)))
+      return rc;
+    const uint64_t* u_cpu = nullptr;
+    const int64_t* u_mem = nullptr;
     if (with_reduce) {
       // the shard's containers [c0, c1) with its CSR offsets rebased to 0
       const int64_t c0 = n > 0 ? node_ptr[lo[sh]] : 0, c1 = n > 0 ? node_ptr[hi[sh]] : 0;
       std::vector<int64_t>& rb = rebased[sh];
       rb.resize((size_t)n + 1);
       for (int64_t k = 0; k <= n; ++k) rb[k] = n > 0 ? node_ptr[lo[sh] + k] - c0 : 0;
-      if ((rc = h2d(ctx, dv, dv.ptr, rb.data(), n + 1))) return rc;
-      if ((rc = h2d(ctx, dv, dv.cpu, cpu_req + c0, c1 - c0))) return rc;
-      if ((rc = h2d(ctx, dv, dv.mem, mem_req + c0, c1 - c0))) return rc;
-      KCC_HIP(ctx, ensure(dv.used_cpu, 8 * (size_t)(n > 0 ? n : 1)));
-      KCC_HIP(ctx, ensure(dv.used_mem, 8 * (size_t)(n > 0 ? n : 1)));
-      if (n > 0) {
-        rc = reduce_async_dev(ctx, dv, n, c1 - c0, as<int64_t>(dv.ptr), as<uint64_t>(dv.cpu),
-                              as<int64_t>(dv.mem), nullptr, nullptr, as<uint64_t>(dv.used_cpu),
-                              as<int64_t>(dv.used_mem), nullptr, nullptr, dv.stream);
-        if (rc) return rc;
-      }
+      const int64_t* ptr = rb.data();
+      const uint64_t* cpu = cpu_req + c0;
+      const int64_t* mem = mem_req + c0;
+      uint64_t* r_cpu = nullptr;
+      int64_t* r_mem = nullptr;
+      if ((rc = st.in(ptr, n + 1)) || (rc = st.in(cpu, c1 - c0)) || (rc = st.in(mem, c1 - c0)) ||
+          (rc = st.tmp(r_cpu, n)) || (rc = st.tmp(r_mem, n)) ||
+          (rc = reduce_async_dev(ctx, dv, n, c1 - c0, ptr, cpu, mem, nullptr, nullptr, r_cpu, r_mem,
+                                 nullptr, nullptr, dv.stream)))
+        return rc;
+      u_cpu = r_cpu;
+      u_mem = r_mem;
     } else {
-      if ((rc = h2d(ctx, dv, dv.used_cpu, used_cpu_in + lo[sh], n))) return rc;
-      if ((rc = h2d(ctx, dv, dv.used_mem, used_mem_in + lo[sh], n))) return rc;
+      u_cpu = used_cpu_in + lo[sh];
+      u_mem = used_mem_in + lo[sh];
+      if ((rc = st.in(u_cpu, n)) || (rc = st.in(u_mem, n))) return rc;
     }
-    rc = fit_partial_dev(ctx, dv, n, as<uint64_t>(dv.alloc_cpu), as<int64_t>(dv.alloc_mem),
-                         as<int64_t>(dv.alloc_pods), as<int64_t>(dv.pod_count),
-                         as<uint64_t>(dv.used_cpu), as<int64_t>(dv.used_mem), n_specs,
-                         as<uint64_t>(dv.spec_cpu), as<int64_t>(dv.spec_mem), part, dv.stream);
+    rc = fit_partial_dev(ctx, dv, n, a_cpu, a_mem, a_pods, pods, u_cpu, u_mem, n_specs, s_cpu, s_mem,
+                         part, dv.stream);
     if (rc) return rc;
     // exact-path pair count of this shard (the next shard's spec setup zeroes it)
     KCC_HIP(ctx, hipMemcpyAsync(ctx->host_cnt + (size_t)sh * kcc::CNT_N, dv.counters.p,
@@ -880,23 +981,20 @@ int run_host(kcc_ctx* ctx, bool with_reduce, int64_t n_nodes, int64_t n_cont,
       ctx->allreduce_verified = true;
     }
   }
+  // finalize on device 0; its stream is synchronised last, by the staging's finish
+  for (int d = nd - 1; d > 0; --d) {
+    KCC_HIP(ctx, hipSetDevice(ctx->devs[d].device));
+    KCC_HIP(ctx, hipStreamSynchronize(ctx->devs[d].stream));
+  }
   Dev& d0 = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(d0.device));
-  KCC_HIP(ctx, ensure(d0.totals, 8 * (size_t)n_specs));
-  KCC_HIP(ctx, ensure(d0.err, 4 * (size_t)n_specs));
-  int rc = fit_finalize_dev(ctx, d0, n_specs, as<int64_t>(d0.partial), as<int64_t>(d0.totals),
-                            as<int32_t>(d0.err), d0.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(totals, d0.totals.p, 8 * (size_t)n_specs, hipMemcpyDeviceToHost,
-                              d0.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(spec_err, d0.err.p, 4 * (size_t)n_specs, hipMemcpyDeviceToHost,
-                              d0.stream));
+  int rc;
+  if ((rc = stages[0].out(totals, n_specs)) || (rc = stages[0].out(spec_err, n_specs)) ||
+      (rc = fit_finalize_dev(ctx, d0, n_specs, as<int64_t>(d0.partial), totals, spec_err,
+                             d0.stream)) ||
+      (rc = stages[0].finish()))
+    return rc;
   unsigned long long slow_pairs = 0;
-  for (int d = 0; d < nd; ++d) {
-    Dev& dv = ctx->devs[d];
-    KCC_HIP(ctx, hipSetDevice(dv.device));
-    KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  }
   int64_t streamed = 0;
   for (int sh = 0; sh < ns; ++sh) {
     slow_pairs += ctx->host_cnt[(size_t)sh * kcc::CNT_N + kcc::CNT_SLOW_PAIRS];
@@ -1010,37 +1108,7 @@ void kcc_destroy(kcc_ctx* ctx) {
       (void)hipDeviceSynchronize();  // exchanges ran on caller streams
       for (int p = 0; p < dv.p2p_W; ++p)
         if (p != dv.p2p_rank && dv.p2p_peer[p]) (void)hipIpcCloseMemHandle(dv.p2p_peer[p]);
-      DevBuf* pb[] = {&dv.p2p_mbox, &dv.p2p_arrive};
-      for (DevBuf* b : pb)
-        if (b->p) (void)hipFree(b->p);
     }
-    if (dv.clamp_arrive.p) (void)hipFree(dv.clamp_arrive.p);
-    if (dv.np_sync.p) (void)hipFree(dv.np_sync.p);
-    DevBuf* bufs[] = {&dv.c_rank, &dv.c_bcnt, &dv.c_cs, &dv.c_ms,
-                      &dv.c_mrc, &dv.c_crm, &dv.c_dperm, &dv.c_C, &dv.c_H2, &dv.c_H3,
-                      &dv.c_Crow, &dv.c_rec, &dv.c_dir,
-                      &dv.red_tail,  &dv.faults, &dv.rank_arrive, &dv.fast_cl, &dv.slow_list, &dv.fast_a, &dv.fast_b, &dv.slow, &dv.srec,
-                      &dv.sperm,     &dv.fit_q,
-                      &dv.counters,  &dv.ptr,       &dv.cpu,       &dv.mem,       &dv.cpul,
-                      &dv.meml,      &dv.used_cpu,  &dv.used_mem,  &dv.lim_cpu,   &dv.lim_mem,
-                      &dv.alloc_cpu, &dv.alloc_mem, &dv.alloc_pods, &dv.pod_count, &dv.spec_cpu,
-                      &dv.spec_mem,  &dv.partial,   &dv.totals,    &dv.err,
-                      &dv.p_bytes,   &dv.p_off,     &dv.p_out,     &dv.p_st,      &dv.k_key,
-                      &dv.kb_counts, &dv.kb_tot,    &dv.kb_sr,     &dv.kb_sv,     &dv.q_ptr,
-                      &dv.kb_part,   &dv.kb_arrive,
-                      &dv.kb_esc_n,  &dv.kb_esc_row, &dv.kb_esc_cpu, &dv.kb_esc_mem,
-                      &dv.q_iptr,    &dv.q_icpu,    &dv.q_imem,    &dv.q_rst,     &dv.q_ocpu,
-                      &dv.q_omem,    &dv.q_pcpu,    &dv.q_pmem,
-                      &dv.g_group,   &dv.g_count,   &dv.g_cursor,  &dv.g_total,   &dv.g_rec,
-                      &dv.g_rg,      &dv.g_acc,     &dv.x_alloc,   &dv.x_used,    &dv.x_spec,
-                      &dv.x_rec,     &dv.sp_qmin,   &dv.sp_cap,    &dv.sp_cmin,   &dv.sp_grows,
-                      &dv.f_cap,     &dv.f_present, &dv.f_flag,    &dv.f_ct,      &dv.f_ce,
-                      &dv.f_gr,      &dv.f_dom,     &dv.f_el,      &dv.f_skew,
-                      &dv.ex_free,   &dv.ex_rows,   &dv.ex_pods,   &dv.ex_left,
-                      &dv.dp_a,      &dv.dp_tsum,   &dv.dp_toff,   &dv.dp_flag,   &dv.dp_st,
-                      &dv.dp_bins,   &dv.dp_el,     &dv.dp_rep,    &dv.dp_nused,  &dv.dp_rows};
-    for (DevBuf* b : bufs)
-      if (b->p) (void)hipFree(b->p);
     if (dv.stream) (void)hipStreamDestroy(dv.stream);
     if (dv.side) {
       (void)hipStreamSynchronize(dv.side);
@@ -1056,7 +1124,7 @@ void kcc_destroy(kcc_ctx* ctx) {
     for (hipEvent_t ev : dv.prof_free) (void)hipEventDestroy(ev);
   }
   if (ctx->host_cnt) (void)hipHostFree(ctx->host_cnt);
-  delete ctx;
+  delete ctx;  // every DevBuf frees its memory: the streams are idle, the peers' handles closed
 }
 
 const char* kcc_last_error(const kcc_ctx* ctx) { return ctx ? ctx->err.c_str() : "NULL context"; }
@@ -1087,46 +1155,26 @@ int kcc_reduce_requests(kcc_ctx* ctx, int64_t n_nodes, int64_t n_containers,
                         const uint64_t* cpu_lim, const int64_t* mem_lim, uint64_t* used_cpu,
                         int64_t* used_mem, uint64_t* lim_cpu, int64_t* lim_mem) {
   if (!ctx) return KCC_EINVAL;
-  int rc = check_csr(ctx, n_nodes, n_containers, node_ptr);
-  if (rc) return rc;
-  if (n_nodes == 0) return KCC_OK;
-  if (!used_cpu || !used_mem) return fail(ctx, KCC_EINVAL, "NULL output");
-  if (n_containers > 0 && (!cpu_req || !mem_req)) return fail(ctx, KCC_EINVAL, "NULL container array");
-  const bool lim = cpu_lim != nullptr || mem_lim != nullptr;
-  if (lim && (!cpu_lim || !mem_lim || !lim_cpu || !lim_mem))
-    return fail(ctx, KCC_EINVAL, "limits need cpu_lim, mem_lim, lim_cpu and lim_mem");
+  int rc = check_reduce(ctx, n_nodes, n_containers, node_ptr, cpu_req, mem_req, cpu_lim, mem_lim,
+                        used_cpu, used_mem, lim_cpu, lim_mem);
+  if (rc || (rc = check_csr(ctx, n_nodes, n_containers, node_ptr))) return rc;
+  if (!cpu_lim) {  // no limits: their sums are not written
+    lim_cpu = nullptr;
+    lim_mem = nullptr;
+  }
   // the reduce is cheap next to the fit: run it on the first device
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = h2d(ctx, dv, dv.ptr, node_ptr, n_nodes + 1))) return rc;
-  if ((rc = h2d(ctx, dv, dv.cpu, cpu_req, n_containers))) return rc;
-  if ((rc = h2d(ctx, dv, dv.mem, mem_req, n_containers))) return rc;
-  if (lim) {
-    if ((rc = h2d(ctx, dv, dv.cpul, cpu_lim, n_containers))) return rc;
-    if ((rc = h2d(ctx, dv, dv.meml, mem_lim, n_containers))) return rc;
-    KCC_HIP(ctx, ensure(dv.lim_cpu, 8 * (size_t)n_nodes));
-    KCC_HIP(ctx, ensure(dv.lim_mem, 8 * (size_t)n_nodes));
-  }
-  KCC_HIP(ctx, ensure(dv.used_cpu, 8 * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.used_mem, 8 * (size_t)n_nodes));
-  rc = reduce_async_dev(ctx, dv, n_nodes, n_containers, as<int64_t>(dv.ptr), as<uint64_t>(dv.cpu),
-                        as<int64_t>(dv.mem), lim ? as<uint64_t>(dv.cpul) : nullptr,
-                        lim ? as<int64_t>(dv.meml) : nullptr, as<uint64_t>(dv.used_cpu),
-                        as<int64_t>(dv.used_mem), lim ? as<uint64_t>(dv.lim_cpu) : nullptr,
-                        lim ? as<int64_t>(dv.lim_mem) : nullptr, dv.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(used_cpu, dv.used_cpu.p, 8 * (size_t)n_nodes,
-                              hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(used_mem, dv.used_mem.p, 8 * (size_t)n_nodes,
-                              hipMemcpyDeviceToHost, dv.stream));
-  if (lim) {
-    KCC_HIP(ctx, hipMemcpyAsync(lim_cpu, dv.lim_cpu.p, 8 * (size_t)n_nodes,
-                                hipMemcpyDeviceToHost, dv.stream));
-    KCC_HIP(ctx, hipMemcpyAsync(lim_mem, dv.lim_mem.p, 8 * (size_t)n_nodes,
-                                hipMemcpyDeviceToHost, dv.stream));
-  }
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return check_faults(ctx);
+  Stage st(ctx, dv);
+  if ((rc = st.in(node_ptr, csr_len(n_nodes))) || (rc = st.in(cpu_req, n_containers)) ||
+      (rc = st.in(mem_req, n_containers)) || (rc = st.in(cpu_lim, n_containers)) ||
+      (rc = st.in(mem_lim, n_containers)) || (rc = st.out(used_cpu, n_nodes)) ||
+      (rc = st.out(used_mem, n_nodes)) || (rc = st.out(lim_cpu, n_nodes)) ||
+      (rc = st.out(lim_mem, n_nodes)) ||
+      (rc = reduce_async_dev(ctx, dv, n_nodes, n_containers, node_ptr, cpu_req, mem_req, cpu_lim,
+                             mem_lim, used_cpu, used_mem, lim_cpu, lim_mem, dv.stream)))
+    return rc;
+  return st.finish(true);
 }
 
 int kcc_fit(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
@@ -1530,12 +1578,19 @@ int kcc_p2p_faults(kcc_ctx* ctx, int64_t* faults) {
 
 namespace {
 
+// Argument checks of the parsers' entry points (host or device pointers alike).
+int check_parse(kcc_ctx* ctx, int64_t n, const char* bytes, int64_t n_bytes,
+                const int64_t* offsets, const int64_t* out, const int8_t* status) {
+  if (n < 0 || n_bytes < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (n > 0 && (!offsets || !out || !status || (n_bytes > 0 && !bytes)))
+    return fail(ctx, KCC_EINVAL, "NULL bytes/offsets/out/status");
+  return KCC_OK;
+}
+
 int parse_async_dev(kcc_ctx* ctx, int mode, int64_t n, const char* bytes, int64_t n_bytes,
                     const int64_t* offsets, int64_t* out, int8_t* status, hipStream_t s) {
-  if (n < 0 || n_bytes < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  if (n == 0) return KCC_OK;
-  if (!offsets || !out || !status || (n_bytes > 0 && !bytes))
-    return fail(ctx, KCC_EINVAL, "NULL bytes/offsets/out/status");
+  const int rc = check_parse(ctx, n, bytes, n_bytes, offsets, out, status);
+  if (rc || n == 0) return rc;
   if ((reinterpret_cast<uintptr_t>(bytes) & 3u) != 0)
     return fail(ctx, KCC_EINVAL, "bytes must be 4-byte aligned");
   KCC_HIP(ctx, kcc::launch_parse(mode, n, reinterpret_cast<const uint8_t*>(bytes), n_bytes,
@@ -1546,28 +1601,20 @@ int parse_async_dev(kcc_ctx* ctx, int mode, int64_t n, const char* bytes, int64_
 int parse_host(kcc_ctx* ctx, int mode, int64_t n, const char* bytes, int64_t n_bytes,
                const int64_t* offsets, int64_t* out, int8_t* status) {
   if (!ctx) return KCC_EINVAL;
-  if (n < 0 || n_bytes < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  if (n == 0) return KCC_OK;
-  if (!offsets || !out || !status || (n_bytes > 0 && !bytes))
-    return fail(ctx, KCC_EINVAL, "NULL bytes/offsets/out/status");
-  if (offsets[0] < 0 || offsets[n] > n_bytes)
+  int rc = check_parse(ctx, n, bytes, n_bytes, offsets, out, status);
+  if (rc) return rc;
+  if (n > 0 && (offsets[0] < 0 || offsets[n] > n_bytes))
     return fail(ctx, KCC_EINVAL, "offsets outside [0, n_bytes]");
   for (int64_t i = 0; i < n; ++i)
     if (offsets[i + 1] < offsets[i]) return fail(ctx, KCC_EINVAL, "offsets are not non-decreasing");
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  int rc;
-  if ((rc = h2d(ctx, dv, dv.p_bytes, bytes, n_bytes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.p_off, offsets, n + 1))) return rc;
-  KCC_HIP(ctx, ensure(dv.p_out, 8 * (size_t)n));
-  KCC_HIP(ctx, ensure(dv.p_st, (size_t)n));
-  rc = parse_async_dev(ctx, mode, n, as<char>(dv.p_bytes), n_bytes, as<int64_t>(dv.p_off),
-                       as<int64_t>(dv.p_out), as<int8_t>(dv.p_st), dv.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(out, dv.p_out.p, 8 * (size_t)n, hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(status, dv.p_st.p, (size_t)n, hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  Stage st(ctx, dv);
+  if ((rc = st.in(bytes, n_bytes)) || (rc = st.in(offsets, csr_len(n))) || (rc = st.out(out, n)) ||
+      (rc = st.out(status, n)) ||
+      (rc = parse_async_dev(ctx, mode, n, bytes, n_bytes, offsets, out, status, dv.stream)))
+    return rc;
+  return st.finish();
 }
 
 }  // namespace
@@ -1672,28 +1719,57 @@ int keyed_work(kcc_ctx* ctx, Dev& dv, int64_t n_keys, int64_t n, int na, kcc::Ke
   return KCC_OK;
 }
 
-int keyed_async_dev(kcc_ctx* ctx, int64_t n_keys, int64_t n, const int32_t* key,
-                    const uint64_t* cpu, const int64_t* mem, const uint64_t* cpul,
-                    const int64_t* meml, uint64_t* used_cpu, int64_t* used_mem, uint64_t* lim_cpu,
-                    int64_t* lim_mem, hipStream_t s) {
+// Argument checks of the keyed reduce's two entry points (host or device pointers alike).
+int check_keyed(kcc_ctx* ctx, int64_t n_keys, int64_t n, const int32_t* key, const uint64_t* cpu,
+                const int64_t* mem, const uint64_t* cpul, const int64_t* meml,
+                const uint64_t* used_cpu, const int64_t* used_mem, const uint64_t* lim_cpu,
+                const int64_t* lim_mem) {
   if (n_keys < 0 || n < 0) return fail(ctx, KCC_EINVAL, "negative size");
   if (n_keys > 0x7fffffff) return fail(ctx, KCC_EINVAL, "more than 2^31 - 1 keys");
   if (n_keys > 0 && (!used_cpu || !used_mem)) return fail(ctx, KCC_EINVAL, "NULL output");
   if (n > 0 && (!key || !cpu || !mem)) return fail(ctx, KCC_EINVAL, "NULL key/cpu_req/mem_req");
-  const bool lim = cpul != nullptr || meml != nullptr;
-  if (lim && (!cpul || !meml || (n_keys > 0 && (!lim_cpu || !lim_mem))))
+  if ((cpul || meml) && (!cpul || !meml || (n_keys > 0 && (!lim_cpu || !lim_mem))))
     return fail(ctx, KCC_EINVAL, "limits need cpu_lim, mem_lim, lim_cpu and lim_mem");
+  return KCC_OK;
+}
+
+int keyed_async_dev(kcc_ctx* ctx, Dev& dv, int64_t n_keys, int64_t n, const int32_t* key,
+                    const uint64_t* cpu, const int64_t* mem, const uint64_t* cpul,
+                    const int64_t* meml, uint64_t* used_cpu, int64_t* used_mem, uint64_t* lim_cpu,
+                    int64_t* lim_mem, hipStream_t s) {
+  int rc = check_keyed(ctx, n_keys, n, key, cpu, mem, cpul, meml, used_cpu, used_mem, lim_cpu,
+                       lim_mem);
+  if (rc) return rc;
+  const bool lim = cpul != nullptr;
   if (!aligned16(key) || !aligned16(cpu) || !aligned16(mem) ||
       (lim && (!aligned16(cpul) || !aligned16(meml))))
     return fail(ctx, KCC_EINVAL, "key and container arrays must be 16-byte aligned");
-  Dev& dv = ctx->devs[0];
   kcc::KeyedWork kw{};
   const kcc::KeyedWork* kwp = nullptr;
-  int rc = keyed_work(ctx, dv, n_keys, n, lim ? 4 : 2, kw, &kwp);
-  if (rc) return rc;
+  if ((rc = keyed_work(ctx, dv, n_keys, n, lim ? 4 : 2, kw, &kwp))) return rc;
   KCC_HIP(ctx, kcc::launch_reduce_keyed(n_keys, n, key, cpu, mem, lim ? cpul : nullptr,
                                         lim ? meml : nullptr, used_cpu, used_mem,
                                         lim ? lim_cpu : nullptr, lim ? lim_mem : nullptr, kwp, s));
+  return KCC_OK;
+}
+
+// Argument checks of kcc_count_by_key's two entry points (host or device pointers alike).
+int check_count(kcc_ctx* ctx, int64_t n_keys, int64_t n, const int32_t* key, const int64_t* count) {
+  if (n_keys < 0 || n < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (n_keys > 0x7fffffff) return fail(ctx, KCC_EINVAL, "more than 2^31 - 1 keys");
+  if ((n_keys > 0 && !count) || (n > 0 && !key)) return fail(ctx, KCC_EINVAL, "NULL key/count");
+  return KCC_OK;
+}
+
+int count_async_dev(kcc_ctx* ctx, Dev& dv, int64_t n_keys, int64_t n, const int32_t* key,
+                    int64_t* count, hipStream_t s) {
+  int rc = check_count(ctx, n_keys, n, key, count);
+  if (rc) return rc;
+  if (!aligned16(key)) return fail(ctx, KCC_EINVAL, "key must be 16-byte aligned");
+  kcc::KeyedWork kw{};
+  const kcc::KeyedWork* kwp = nullptr;
+  if ((rc = keyed_work(ctx, dv, n_keys, n, 0, kw, &kwp))) return rc;
+  KCC_HIP(ctx, kcc::launch_count_keyed(n_keys, n, key, count, kwp, s));
   return KCC_OK;
 }
 
@@ -1710,7 +1786,7 @@ int kcc_reduce_requests_keyed_async(kcc_ctx* ctx, int64_t n_keys, int64_t n_cont
   if (!ctx) return KCC_EINVAL;
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  return keyed_async_dev(ctx, n_keys, n_containers, d_key, d_cpu_req, d_mem_req, d_cpu_lim,
+  return keyed_async_dev(ctx, dv, n_keys, n_containers, d_key, d_cpu_req, d_mem_req, d_cpu_lim,
                          d_mem_lim, d_used_cpu, d_used_mem, d_lim_cpu, d_lim_mem,
                          static_cast<hipStream_t>(stream));
 }
@@ -1721,85 +1797,46 @@ int kcc_reduce_requests_keyed(kcc_ctx* ctx, int64_t n_keys, int64_t n_containers
                               uint64_t* used_cpu, int64_t* used_mem, uint64_t* lim_cpu,
                               int64_t* lim_mem) {
   if (!ctx) return KCC_EINVAL;
-  if (n_keys < 0 || n_containers < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  if (n_keys > 0 && (!used_cpu || !used_mem)) return fail(ctx, KCC_EINVAL, "NULL output");
-  if (n_containers > 0 && (!key || !cpu_req || !mem_req))
-    return fail(ctx, KCC_EINVAL, "NULL key/cpu_req/mem_req");
-  const bool lim = cpu_lim != nullptr || mem_lim != nullptr;
-  if (lim && (!cpu_lim || !mem_lim || (n_keys > 0 && (!lim_cpu || !lim_mem))))
-    return fail(ctx, KCC_EINVAL, "limits need cpu_lim, mem_lim, lim_cpu and lim_mem");
-  if (n_keys == 0) return KCC_OK;
+  int rc = check_keyed(ctx, n_keys, n_containers, key, cpu_req, mem_req, cpu_lim, mem_lim, used_cpu,
+                       used_mem, lim_cpu, lim_mem);
+  if (rc) return rc;
+  if (!cpu_lim) {  // no limits: their sums are not written
+    lim_cpu = nullptr;
+    lim_mem = nullptr;
+  }
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  int rc;
-  if ((rc = h2d(ctx, dv, dv.k_key, key, n_containers))) return rc;
-  if ((rc = h2d(ctx, dv, dv.cpu, cpu_req, n_containers))) return rc;
-  if ((rc = h2d(ctx, dv, dv.mem, mem_req, n_containers))) return rc;
-  if (lim) {
-    if ((rc = h2d(ctx, dv, dv.cpul, cpu_lim, n_containers))) return rc;
-    if ((rc = h2d(ctx, dv, dv.meml, mem_lim, n_containers))) return rc;
-    KCC_HIP(ctx, ensure(dv.lim_cpu, 8 * (size_t)n_keys));
-    KCC_HIP(ctx, ensure(dv.lim_mem, 8 * (size_t)n_keys));
-  }
-  KCC_HIP(ctx, ensure(dv.used_cpu, 8 * (size_t)n_keys));
-  KCC_HIP(ctx, ensure(dv.used_mem, 8 * (size_t)n_keys));
-  rc = keyed_async_dev(ctx, n_keys, n_containers, as<int32_t>(dv.k_key), as<uint64_t>(dv.cpu),
-                       as<int64_t>(dv.mem), lim ? as<uint64_t>(dv.cpul) : nullptr,
-                       lim ? as<int64_t>(dv.meml) : nullptr, as<uint64_t>(dv.used_cpu),
-                       as<int64_t>(dv.used_mem), lim ? as<uint64_t>(dv.lim_cpu) : nullptr,
-                       lim ? as<int64_t>(dv.lim_mem) : nullptr, dv.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(used_cpu, dv.used_cpu.p, 8 * (size_t)n_keys, hipMemcpyDeviceToHost,
-                              dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(used_mem, dv.used_mem.p, 8 * (size_t)n_keys, hipMemcpyDeviceToHost,
-                              dv.stream));
-  if (lim) {
-    KCC_HIP(ctx, hipMemcpyAsync(lim_cpu, dv.lim_cpu.p, 8 * (size_t)n_keys,
-                                hipMemcpyDeviceToHost, dv.stream));
-    KCC_HIP(ctx, hipMemcpyAsync(lim_mem, dv.lim_mem.p, 8 * (size_t)n_keys,
-                                hipMemcpyDeviceToHost, dv.stream));
-  }
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return check_faults(ctx);
+  Stage st(ctx, dv);
+  if ((rc = st.in(key, n_containers)) || (rc = st.in(cpu_req, n_containers)) ||
+      (rc = st.in(mem_req, n_containers)) || (rc = st.in(cpu_lim, n_containers)) ||
+      (rc = st.in(mem_lim, n_containers)) || (rc = st.out(used_cpu, n_keys)) ||
+      (rc = st.out(used_mem, n_keys)) || (rc = st.out(lim_cpu, n_keys)) ||
+      (rc = st.out(lim_mem, n_keys)) ||
+      (rc = keyed_async_dev(ctx, dv, n_keys, n_containers, key, cpu_req, mem_req, cpu_lim, mem_lim,
+                            used_cpu, used_mem, lim_cpu, lim_mem, dv.stream)))
+    return rc;
+  return st.finish(true);
 }
 
 int kcc_count_by_key_async(kcc_ctx* ctx, int64_t n_keys, int64_t n, const int32_t* d_key,
                            int64_t* d_count, void* stream) {
   if (!ctx) return KCC_EINVAL;
-  if (n_keys < 0 || n < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  if (n_keys > 0x7fffffff) return fail(ctx, KCC_EINVAL, "more than 2^31 - 1 keys");
-  if ((n_keys > 0 && !d_count) || (n > 0 && !d_key)) return fail(ctx, KCC_EINVAL, "NULL key/count");
-  if (!aligned16(d_key)) return fail(ctx, KCC_EINVAL, "key must be 16-byte aligned");
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  kcc::KeyedWork kw{};
-  const kcc::KeyedWork* kwp = nullptr;
-  int rc = keyed_work(ctx, dv, n_keys, n, 0, kw, &kwp);
-  if (rc) return rc;
-  KCC_HIP(ctx, kcc::launch_count_keyed(n_keys, n, d_key, d_count, kwp,
-                                       static_cast<hipStream_t>(stream)));
-  return KCC_OK;
+  return count_async_dev(ctx, dv, n_keys, n, d_key, d_count, static_cast<hipStream_t>(stream));
 }
 
 int kcc_count_by_key(kcc_ctx* ctx, int64_t n_keys, int64_t n, const int32_t* key, int64_t* count) {
   if (!ctx) return KCC_EINVAL;
-  if (n_keys < 0 || n < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  if ((n_keys > 0 && !count) || (n > 0 && !key)) return fail(ctx, KCC_EINVAL, "NULL key/count");
-  if (n_keys == 0) return KCC_OK;
+  int rc = check_count(ctx, n_keys, n, key, count);
+  if (rc) return rc;
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  int rc;
-  if ((rc = h2d(ctx, dv, dv.k_key, key, n))) return rc;
-  KCC_HIP(ctx, ensure(dv.pod_count, 8 * (size_t)n_keys));
-  kcc::KeyedWork kw{};
-  const kcc::KeyedWork* kwp = nullptr;
-  if ((rc = keyed_work(ctx, dv, n_keys, n, 0, kw, &kwp))) return rc;
-  KCC_HIP(ctx, kcc::launch_count_keyed(n_keys, n, as<int32_t>(dv.k_key), as<int64_t>(dv.pod_count),
-                                       kwp, dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(count, dv.pod_count.p, 8 * (size_t)n_keys, hipMemcpyDeviceToHost,
-                              dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return check_faults(ctx);
+  Stage st(ctx, dv);
+  if ((rc = st.in(key, n)) || (rc = st.out(count, n_keys)) ||
+      (rc = count_async_dev(ctx, dv, n_keys, n, key, count, dv.stream)))
+    return rc;
+  return st.finish(true);
 }
 
 }  // extern "C"
@@ -1820,26 +1857,16 @@ extern "C" int kcc_fit_rows(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc
     return fail(ctx, KCC_EINVAL, "NULL node array / output");
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
+  Stage st(ctx, dv);
   int rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_cpu, alloc_cpu, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_mem, alloc_mem, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.alloc_pods, alloc_pods, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.pod_count, pod_count, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.used_cpu, used_cpu, n_nodes))) return rc;
-  if ((rc = h2d(ctx, dv, dv.used_mem, used_mem, n_nodes))) return rc;
-  KCC_HIP(ctx, ensure(dv.totals, 8 * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.err, 4 * (size_t)n_nodes));
-  KCC_HIP(ctx, kcc::launch_fit_rows(n_nodes, as<uint64_t>(dv.alloc_cpu), as<int64_t>(dv.alloc_mem),
-                                    as<int64_t>(dv.alloc_pods), as<int64_t>(dv.pod_count),
-                                    as<uint64_t>(dv.used_cpu), as<int64_t>(dv.used_mem), spec_cpu,
-                                    spec_mem, as<int64_t>(dv.totals), as<int32_t>(dv.err),
-                                    dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(q, dv.totals.p, 8 * (size_t)n_nodes, hipMemcpyDeviceToHost,
-                              dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(row_err, dv.err.p, 4 * (size_t)n_nodes, hipMemcpyDeviceToHost,
-                              dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  if ((rc = st.in(alloc_cpu, n_nodes)) || (rc = st.in(alloc_mem, n_nodes)) ||
+      (rc = st.in(alloc_pods, n_nodes)) || (rc = st.in(pod_count, n_nodes)) ||
+      (rc = st.in(used_cpu, n_nodes)) || (rc = st.in(used_mem, n_nodes)) ||
+      (rc = st.out(q, n_nodes)) || (rc = st.out(row_err, n_nodes)))
+    return rc;
+  KCC_HIP(ctx, kcc::launch_fit_rows(n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
+                                    used_mem, spec_cpu, spec_mem, q, row_err, dv.stream));
+  return st.finish();
 }
 
 
@@ -1925,70 +1952,37 @@ int fit_cells_async(kcc_ctx* ctx, const kcc::FitNodes& nd, const kcc::FitSpecs& 
                        static_cast<hipStream_t>(stream));
 }
 
-// The host array p (nullable: NULL stays NULL) copied to buf; p then names the device copy.
-template <class T>
-int stage(kcc_ctx* ctx, Dev& dv, DevBuf& buf, const T*& p, int64_t count) {
-  if (!p) return KCC_OK;
-  const int rc = h2d(ctx, dv, buf, p, count);
-  p = as<T>(buf);
-  return rc;
+// The cell fits' thirteen input arrays, staged.
+int stage_cells(Stage& st, kcc::FitNodes& nd, kcc::FitSpecs& sp) {
+  const int64_t n = nd.n, S = sp.S;
+  int rc;
+  if ((rc = st.in(nd.alloc_cpu, n)) || (rc = st.in(nd.alloc_mem, n)) ||
+      (rc = st.in(nd.alloc_pods, n)) || (rc = st.in(nd.pod_count, n)) ||
+      (rc = st.in(nd.used_cpu, n)) || (rc = st.in(nd.used_mem, n)) ||
+      (rc = st.in(nd.alloc_x, nd.R * n)) || (rc = st.in(nd.used_x, nd.R * n)) ||
+      (rc = st.in(nd.group, n)) || (rc = st.in(sp.spec_cpu, S)) || (rc = st.in(sp.spec_mem, S)) ||
+      (rc = st.in(sp.spec_x, nd.R * S)) || (rc = st.in(sp.node_cap, S)))
+    return rc;
+  return KCC_OK;
 }
 
-// Host level: stages the inputs, runs fit_cells_dev, copies the outputs back and syncs.
+// Host level: checks, stages, runs fit_cells_dev and copies the outputs back.
 int fit_cells_host(kcc_ctx* ctx, kcc::FitNodes nd, kcc::FitSpecs sp, bool need_group,
                    int64_t* totals, int32_t* spec_err, int64_t* cell_min, int64_t* group_rows) {
   if (!ctx) return KCC_EINVAL;
   int rc = check_cells(ctx, nd, sp, need_group, totals, spec_err);
   if (rc) return rc;
-  const int64_t n = nd.n, S = sp.S;
-  const size_t cells = (size_t)(nd.G * S);
-  if (n == 0) {
-    if (S > 0) {
-      memset(totals, 0, 8 * cells);
-      memset(spec_err, 0, 4 * cells);
-      if (cell_min)
-        for (size_t k = 0; k < cells; ++k) cell_min[k] = INT64_MAX;
-    }
-    if (group_rows) memset(group_rows, 0, 8 * (size_t)nd.G);
-    return KCC_OK;
-  }
-  if (S == 0 && !group_rows) return KCC_OK;
+  const int64_t cells = nd.G * sp.S;
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = stage(ctx, dv, dv.alloc_cpu, nd.alloc_cpu, n)) ||
-      (rc = stage(ctx, dv, dv.alloc_mem, nd.alloc_mem, n)) ||
-      (rc = stage(ctx, dv, dv.alloc_pods, nd.alloc_pods, n)) ||
-      (rc = stage(ctx, dv, dv.pod_count, nd.pod_count, n)) ||
-      (rc = stage(ctx, dv, dv.used_cpu, nd.used_cpu, n)) ||
-      (rc = stage(ctx, dv, dv.used_mem, nd.used_mem, n)) ||
-      (rc = stage(ctx, dv, dv.x_alloc, nd.alloc_x, nd.R * n)) ||
-      (rc = stage(ctx, dv, dv.x_used, nd.used_x, nd.R * n)) ||
-      (rc = stage(ctx, dv, dv.g_group, nd.group, n)) ||
-      (rc = stage(ctx, dv, dv.spec_cpu, sp.spec_cpu, S)) ||
-      (rc = stage(ctx, dv, dv.spec_mem, sp.spec_mem, S)) ||
-      (rc = stage(ctx, dv, dv.x_spec, sp.spec_x, nd.R * S)) ||
-      (rc = stage(ctx, dv, dv.sp_cap, sp.node_cap, S)))
+  Stage st(ctx, dv);
+  if ((rc = stage_cells(st, nd, sp)) || (rc = st.out(totals, cells)) ||
+      (rc = st.out(spec_err, cells)) || (rc = st.out(cell_min, cells)) ||
+      (rc = st.out(group_rows, nd.G)) ||
+      (rc = fit_cells_dev(ctx, dv, nd, sp, need_group, totals, spec_err, cell_min, group_rows,
+                          dv.stream)))
     return rc;
-  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
-  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
-  if (cell_min) KCC_HIP(ctx, ensure(dv.sp_cmin, 8 * cells));
-  if (group_rows) KCC_HIP(ctx, ensure(dv.sp_grows, 8 * (size_t)nd.G));
-  rc = fit_cells_dev(ctx, dv, nd, sp, need_group, as<int64_t>(dv.totals), as<int32_t>(dv.err),
-                     cell_min ? as<int64_t>(dv.sp_cmin) : nullptr,
-                     group_rows ? as<int64_t>(dv.sp_grows) : nullptr, dv.stream);
-  if (rc) return rc;
-  if (S > 0) {
-    KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
-    KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
-    if (cell_min)
-      KCC_HIP(ctx, hipMemcpyAsync(cell_min, dv.sp_cmin.p, 8 * cells, hipMemcpyDeviceToHost,
-                                  dv.stream));
-  }
-  if (group_rows)
-    KCC_HIP(ctx, hipMemcpyAsync(group_rows, dv.sp_grows.p, 8 * (size_t)nd.G,
-                                hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  return st.finish();
 }
 
 }  // namespace
@@ -2175,59 +2169,19 @@ int kcc_fit_explain(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
   kcc::FitNodes nd{n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
                    n_ext, alloc_x, used_x, group, n_groups};
   kcc::FitSpecs sp{n_specs, spec_cpu, spec_mem, spec_x, node_cap};
-  const ExplainOut o{why_rows, why_pods, left};
+  ExplainOut o{why_rows, why_pods, left};
   int rc = check_explain(ctx, nd, sp, totals, spec_err, o);
   if (rc) return rc;
-  if (!why_rows && !why_pods && !left)  // kcc_fit_capped itself
-    return fit_cells_host(ctx, nd, sp, false, totals, spec_err, nullptr, nullptr);
-  const int64_t n = n_nodes, S = n_specs;
-  if (S == 0) return KCC_OK;
-  const size_t cells = (size_t)(n_groups * S);
-  const size_t why_bytes = 8 * (size_t)KCC_WHY_SLOTS * cells, left_bytes = 8 * (size_t)(2 + n_ext) * cells;
-  if (n == 0) {
-    memset(totals, 0, 8 * cells);
-    memset(spec_err, 0, 4 * cells);
-    if (why_rows) memset(why_rows, 0, why_bytes);
-    if (why_pods) memset(why_pods, 0, why_bytes);
-    if (left) memset(left, 0, left_bytes);
-    return KCC_OK;
-  }
+  const int64_t cells = n_groups * n_specs;
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = stage(ctx, dv, dv.alloc_cpu, nd.alloc_cpu, n)) ||
-      (rc = stage(ctx, dv, dv.alloc_mem, nd.alloc_mem, n)) ||
-      (rc = stage(ctx, dv, dv.alloc_pods, nd.alloc_pods, n)) ||
-      (rc = stage(ctx, dv, dv.pod_count, nd.pod_count, n)) ||
-      (rc = stage(ctx, dv, dv.used_cpu, nd.used_cpu, n)) ||
-      (rc = stage(ctx, dv, dv.used_mem, nd.used_mem, n)) ||
-      (rc = stage(ctx, dv, dv.x_alloc, nd.alloc_x, nd.R * n)) ||
-      (rc = stage(ctx, dv, dv.x_used, nd.used_x, nd.R * n)) ||
-      (rc = stage(ctx, dv, dv.g_group, nd.group, n)) ||
-      (rc = stage(ctx, dv, dv.spec_cpu, sp.spec_cpu, S)) ||
-      (rc = stage(ctx, dv, dv.spec_mem, sp.spec_mem, S)) ||
-      (rc = stage(ctx, dv, dv.x_spec, sp.spec_x, nd.R * S)) ||
-      (rc = stage(ctx, dv, dv.sp_cap, sp.node_cap, S)))
+  Stage st(ctx, dv);
+  if ((rc = stage_cells(st, nd, sp)) || (rc = st.out(totals, cells)) ||
+      (rc = st.out(spec_err, cells)) || (rc = st.out(o.why_rows, KCC_WHY_SLOTS * cells)) ||
+      (rc = st.out(o.why_pods, KCC_WHY_SLOTS * cells)) || (rc = st.out(o.left, (2 + n_ext) * cells)) ||
+      (rc = fit_explain_dev(ctx, dv, nd, sp, totals, spec_err, o, dv.stream)))
     return rc;
-  KCC_HIP(ctx, ensure(dv.totals, 8 * cells));
-  KCC_HIP(ctx, ensure(dv.err, 4 * cells));
-  if (why_rows) KCC_HIP(ctx, ensure(dv.ex_rows, why_bytes));
-  if (why_pods) KCC_HIP(ctx, ensure(dv.ex_pods, why_bytes));
-  if (left) KCC_HIP(ctx, ensure(dv.ex_left, left_bytes));
-  const ExplainOut d{why_rows ? as<int64_t>(dv.ex_rows) : nullptr,
-                     why_pods ? as<int64_t>(dv.ex_pods) : nullptr,
-                     left ? as<int64_t>(dv.ex_left) : nullptr};
-  rc = fit_explain_dev(ctx, dv, nd, sp, as<int64_t>(dv.totals), as<int32_t>(dv.err), d, dv.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * cells, hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * cells, hipMemcpyDeviceToHost, dv.stream));
-  if (why_rows)
-    KCC_HIP(ctx, hipMemcpyAsync(why_rows, dv.ex_rows.p, why_bytes, hipMemcpyDeviceToHost, dv.stream));
-  if (why_pods)
-    KCC_HIP(ctx, hipMemcpyAsync(why_pods, dv.ex_pods.p, why_bytes, hipMemcpyDeviceToHost, dv.stream));
-  if (left)
-    KCC_HIP(ctx, hipMemcpyAsync(left, dv.ex_left.p, left_bytes, hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  return st.finish();
 }
 
 }  // extern "C"
@@ -2237,17 +2191,13 @@ int kcc_fit_explain(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
 
 namespace {
 
-// Argument checks of both fold entry points.  *degenerate: nothing to launch.
+// Argument checks of both fold entry points (host or device pointers alike).
 int check_fold(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs, const int64_t* cell_totals,
                const int32_t* cell_err, const int32_t* domain_of, int64_t n_domains,
-               const int64_t* totals, const int32_t* spec_err, bool* degenerate) {
-  *degenerate = false;
+               const int64_t* totals, const int32_t* spec_err) {
   if (n_groups < 0 || n_specs < 0) return fail(ctx, KCC_EINVAL, "negative size");
   if (n_specs > 0 && (!totals || !spec_err)) return fail(ctx, KCC_EINVAL, "NULL output");
-  if (n_groups == 0 || n_specs == 0) {
-    *degenerate = true;
-    return KCC_OK;
-  }
+  if (n_groups == 0 || n_specs == 0) return KCC_OK;  // no cells: nothing else is looked at
   if (n_domains < 1) return fail(ctx, KCC_EINVAL, "n_domains must be at least 1");
   if (!domain_of && n_domains != n_groups)
     return fail(ctx, KCC_EINVAL, "domain_of is NULL: n_domains must equal n_groups");
@@ -2264,15 +2214,12 @@ int spread_fold_dev(kcc_ctx* ctx, Dev& dv, int64_t n_groups, int64_t n_specs,
                     const int64_t* group_rows, const int32_t* domain_of, int64_t n_domains,
                     const uint8_t* eligible, const int64_t* max_skew, int64_t* totals,
                     int32_t* spec_err, hipStream_t s) {
-  bool degenerate;
   int rc = check_fold(ctx, n_groups, n_specs, cell_totals, cell_err, domain_of, n_domains, totals,
-                      spec_err, &degenerate);
-  if (rc) return rc;
-  if (degenerate) {
-    if (n_specs > 0) {
-      KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * (size_t)n_specs, s));
-      KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * (size_t)n_specs, s));
-    }
+                      spec_err);
+  if (rc || n_specs == 0) return rc;
+  if (n_groups == 0) {  // no cells: every total 0, no spec flagged
+    KCC_HIP(ctx, hipMemsetAsync(totals, 0, 8 * (size_t)n_specs, s));
+    KCC_HIP(ctx, hipMemsetAsync(spec_err, 0, 4 * (size_t)n_specs, s));
     return KCC_OK;
   }
   const size_t dcells = (size_t)(n_domains * n_specs);
@@ -2308,41 +2255,22 @@ int kcc_spread_fold(kcc_ctx* ctx, int64_t n_groups, int64_t n_specs, const int64
                     int64_t n_domains, const uint8_t* eligible, const int64_t* max_skew,
                     int64_t* totals, int32_t* spec_err) {
   if (!ctx) return KCC_EINVAL;
-  bool degenerate;
   int rc = check_fold(ctx, n_groups, n_specs, cell_totals, cell_err, domain_of, n_domains, totals,
-                      spec_err, &degenerate);
+                      spec_err);
   if (rc) return rc;
-  if (degenerate) {
-    if (n_specs > 0) {
-      memset(totals, 0, 8 * (size_t)n_specs);
-      memset(spec_err, 0, 4 * (size_t)n_specs);
-    }
-    return KCC_OK;
-  }
   const int64_t cells = n_groups * n_specs;
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = h2d(ctx, dv, dv.f_ct, cell_totals, cells))) return rc;
-  if ((rc = h2d(ctx, dv, dv.f_ce, cell_err, cells))) return rc;
-  if (group_rows && (rc = h2d(ctx, dv, dv.f_gr, group_rows, n_groups))) return rc;
-  if (domain_of && (rc = h2d(ctx, dv, dv.f_dom, domain_of, n_groups))) return rc;
-  if (eligible && (rc = h2d(ctx, dv, dv.f_el, eligible, cells))) return rc;
-  if (max_skew && (rc = h2d(ctx, dv, dv.f_skew, max_skew, n_specs))) return rc;
-  KCC_HIP(ctx, ensure(dv.totals, 8 * (size_t)n_specs));
-  KCC_HIP(ctx, ensure(dv.err, 4 * (size_t)n_specs));
-  rc = spread_fold_dev(ctx, dv, n_groups, n_specs, as<int64_t>(dv.f_ct), as<int32_t>(dv.f_ce),
-                       group_rows ? as<int64_t>(dv.f_gr) : nullptr,
-                       domain_of ? as<int32_t>(dv.f_dom) : nullptr, n_domains,
-                       eligible ? as<uint8_t>(dv.f_el) : nullptr,
-                       max_skew ? as<int64_t>(dv.f_skew) : nullptr, as<int64_t>(dv.totals),
-                       as<int32_t>(dv.err), dv.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(totals, dv.totals.p, 8 * (size_t)n_specs, hipMemcpyDeviceToHost,
-                              dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(spec_err, dv.err.p, 4 * (size_t)n_specs, hipMemcpyDeviceToHost,
-                              dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  Stage st(ctx, dv);
+  if ((rc = st.in(cell_totals, cells)) || (rc = st.in(cell_err, cells)) ||
+      (rc = st.in(group_rows, n_groups)) || (rc = st.in(domain_of, n_groups)) ||
+      (rc = st.in(eligible, cells)) || (rc = st.in(max_skew, n_specs)) ||
+      (rc = st.out(totals, n_specs)) || (rc = st.out(spec_err, n_specs)) ||
+      (rc = spread_fold_dev(ctx, dv, n_groups, n_specs, cell_totals, cell_err, group_rows,
+                            domain_of, n_domains, eligible, max_skew, totals, spec_err,
+                            dv.stream)))
+    return rc;
+  return st.finish();
 }
 
 }  // extern "C"
@@ -2391,8 +2319,17 @@ int check_deploy(kcc_ctx* ctx, const DeployArgs& a) {
   return KCC_OK;
 }
 
-// Device level: the workspaces (they only grow) and the launches on s.  n, K >= 1.
+// Device level: the checks, the degenerate cases, the workspaces (they only grow) and the
+// launches on s.
 int deploy_dev(kcc_ctx* ctx, Dev& dv, const DeployArgs& a, hipStream_t s) {
+  const int rc = check_deploy(ctx, a);
+  if (rc || a.plan.K == 0) return rc;  // no steps: nothing is written
+  if (a.nd.n == 0) {  // no rows: nothing placed, no step flagged
+    KCC_HIP(ctx, hipMemsetAsync(a.placed, 0, 8 * (size_t)a.plan.K, s));
+    KCC_HIP(ctx, hipMemsetAsync(a.nodes_used, 0, 8 * (size_t)a.plan.K, s));
+    KCC_HIP(ctx, hipMemsetAsync(a.step_err, 0, 4 * (size_t)a.plan.K, s));
+    return KCC_OK;
+  }
   const size_t tiles = (size_t)kcc::deploy_tiles(a.nd.n), K = (size_t)a.plan.K;
   KCC_HIP(ctx, ensure(dv.dp_a, 4 * (size_t)a.nd.n));
   KCC_HIP(ctx, ensure(dv.dp_tsum, 8 * tiles));
@@ -2405,14 +2342,6 @@ int deploy_dev(kcc_ctx* ctx, Dev& dv, const DeployArgs& a, hipStream_t s) {
                           as<uint32_t>(dv.dp_flag), as<uint64_t>(dv.dp_st),   as<uint64_t>(dv.dp_bins)};
   KCC_HIP(ctx, kcc::launch_deploy(a.nd, a.pod_count, a.used_cpu, a.used_mem, a.used_x, a.eligible,
                                   a.plan, w, a.placed, a.nodes_used, a.step_err, a.placed_rows, s));
-  return KCC_OK;
-}
-
-template <class T>
-int d2h(kcc_ctx* ctx, Dev& dv, T* dst, const DevBuf& buf, int64_t count) {
-  if (count > 0)
-    KCC_HIP(ctx, hipMemcpyAsync(dst, buf.p, sizeof(T) * (size_t)count, hipMemcpyDeviceToHost,
-                                dv.stream));
   return KCC_OK;
 }
 
@@ -2436,19 +2365,9 @@ int kcc_deploy_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
                      d_pod_count, d_used_cpu, d_used_mem, d_used_x, d_eligible,
                      {n_steps, d_spec_cpu, d_spec_mem, d_spec_x, d_replicas, d_node_cap, policy},
                      d_placed, d_nodes_used, d_step_err, d_placed_rows};
-  int rc = check_deploy(ctx, a);
-  if (rc) return rc;
-  if (n_steps == 0) return KCC_OK;
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n_nodes == 0) {  // no rows: nothing placed, no step flagged
-    KCC_HIP(ctx, hipMemsetAsync(d_placed, 0, 8 * (size_t)n_steps, s));
-    KCC_HIP(ctx, hipMemsetAsync(d_nodes_used, 0, 8 * (size_t)n_steps, s));
-    KCC_HIP(ctx, hipMemsetAsync(d_step_err, 0, 4 * (size_t)n_steps, s));
-    return KCC_OK;
-  }
-  return deploy_dev(ctx, dv, a, s);
+  return deploy_dev(ctx, dv, a, static_cast<hipStream_t>(stream));
 }
 
 int kcc_deploy(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
@@ -2467,52 +2386,21 @@ int kcc_deploy(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const i
   int rc = check_deploy(ctx, a);
   if (rc) return rc;
   const int64_t n = n_nodes, K = n_steps, R = n_ext;
-  if (K == 0) return KCC_OK;
-  if (n == 0) {
-    memset(placed, 0, 8 * (size_t)K);
-    memset(nodes_used, 0, 8 * (size_t)K);
-    memset(step_err, 0, 4 * (size_t)K);
-    return KCC_OK;
-  }
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = stage(ctx, dv, dv.alloc_cpu, a.nd.alloc_cpu, n)) ||
-      (rc = stage(ctx, dv, dv.alloc_mem, a.nd.alloc_mem, n)) ||
-      (rc = stage(ctx, dv, dv.alloc_pods, a.nd.alloc_pods, n)) ||
-      (rc = stage(ctx, dv, dv.x_alloc, a.nd.alloc_x, R * n)) ||
-      (rc = stage(ctx, dv, dv.g_group, a.nd.group, n)) ||
-      (rc = stage(ctx, dv, dv.dp_el, a.eligible, n_groups * K)) ||
-      (rc = stage(ctx, dv, dv.spec_cpu, a.plan.spec_cpu, K)) ||
-      (rc = stage(ctx, dv, dv.spec_mem, a.plan.spec_mem, K)) ||
-      (rc = stage(ctx, dv, dv.x_spec, a.plan.spec_x, R * K)) ||
-      (rc = stage(ctx, dv, dv.dp_rep, a.plan.replicas, K)) ||
-      (rc = stage(ctx, dv, dv.sp_cap, a.plan.node_cap, K)) ||
-      (rc = h2d(ctx, dv, dv.pod_count, pod_count, n)) ||
-      (rc = h2d(ctx, dv, dv.used_cpu, used_cpu, n)) ||
-      (rc = h2d(ctx, dv, dv.used_mem, used_mem, n)) ||
-      (R > 0 && (rc = h2d(ctx, dv, dv.x_used, used_x, R * n))))
+  Stage st(ctx, dv);
+  if ((rc = st.in(a.nd.alloc_cpu, n)) || (rc = st.in(a.nd.alloc_mem, n)) ||
+      (rc = st.in(a.nd.alloc_pods, n)) || (rc = st.in(a.nd.alloc_x, R * n)) ||
+      (rc = st.in(a.nd.group, n)) || (rc = st.in(a.eligible, n_groups * K)) ||
+      (rc = st.in(a.plan.spec_cpu, K)) || (rc = st.in(a.plan.spec_mem, K)) ||
+      (rc = st.in(a.plan.spec_x, R * K)) || (rc = st.in(a.plan.replicas, K)) ||
+      (rc = st.in(a.plan.node_cap, K)) || (rc = st.inout(a.pod_count, n)) ||
+      (rc = st.inout(a.used_cpu, n)) || (rc = st.inout(a.used_mem, n)) ||
+      (rc = st.inout(a.used_x, R * n)) || (rc = st.out(a.placed, K)) ||
+      (rc = st.out(a.nodes_used, K)) || (rc = st.out(a.step_err, K)) ||
+      (rc = st.out(a.placed_rows, K * n)) || (rc = deploy_dev(ctx, dv, a, dv.stream)))
     return rc;
-  KCC_HIP(ctx, ensure(dv.totals, 8 * (size_t)K));
-  KCC_HIP(ctx, ensure(dv.dp_nused, 8 * (size_t)K));
-  KCC_HIP(ctx, ensure(dv.err, 4 * (size_t)K));
-  if (placed_rows) KCC_HIP(ctx, ensure(dv.dp_rows, 8 * (size_t)K * (size_t)n));
-  a.pod_count = as<int64_t>(dv.pod_count);
-  a.used_cpu = as<uint64_t>(dv.used_cpu);
-  a.used_mem = as<int64_t>(dv.used_mem);
-  a.used_x = R > 0 ? as<int64_t>(dv.x_used) : nullptr;
-  a.placed = as<int64_t>(dv.totals);
-  a.nodes_used = as<int64_t>(dv.dp_nused);
-  a.step_err = as<int32_t>(dv.err);
-  a.placed_rows = placed_rows ? as<int64_t>(dv.dp_rows) : nullptr;
-  if ((rc = deploy_dev(ctx, dv, a, dv.stream))) return rc;
-  if ((rc = d2h(ctx, dv, placed, dv.totals, K)) || (rc = d2h(ctx, dv, nodes_used, dv.dp_nused, K)) ||
-      (rc = d2h(ctx, dv, step_err, dv.err, K)) || (rc = d2h(ctx, dv, pod_count, dv.pod_count, n)) ||
-      (rc = d2h(ctx, dv, used_cpu, dv.used_cpu, n)) || (rc = d2h(ctx, dv, used_mem, dv.used_mem, n)) ||
-      (R > 0 && (rc = d2h(ctx, dv, used_x, dv.x_used, R * n))) ||
-      (placed_rows && (rc = d2h(ctx, dv, placed_rows, dv.dp_rows, K * n))))
-    return rc;
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  return st.finish();
 }
 
 }  // extern "C"
@@ -2522,54 +2410,65 @@ int kcc_deploy(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const i
 
 namespace {
 
-// Host-side checks shared by the two host-array entry points.
-int check_pods(kcc_ctx* ctx, int64_t n_pods, int64_t n_cont, int64_t n_init,
-               const int64_t* pod_ptr, const uint64_t* cpu_req, const int64_t* mem_req,
-               const int64_t* init_ptr, const uint64_t* init_cpu, const int64_t* init_mem,
-               const uint8_t* restartable) {
-  int rc = check_csr(ctx, n_pods, n_cont, pod_ptr);
-  if (rc) return rc;
-  if (n_cont > 0 && (!cpu_req || !mem_req)) return fail(ctx, KCC_EINVAL, "NULL cpu_req/mem_req");
-  if (!init_ptr) {
-    if (n_init != 0 || init_cpu || init_mem || restartable)
-      return fail(ctx, KCC_EINVAL, "init container arrays without init_ptr");
-    return KCC_OK;
-  }
-  if ((rc = check_csr(ctx, n_pods, n_init, init_ptr))) return rc;
-  if (n_init > 0 && (!init_cpu || !init_mem)) return fail(ctx, KCC_EINVAL, "NULL init_cpu/init_mem");
+struct PodArgs {
+  int64_t n_pods, n_cont, n_init;
+  const int64_t* pod_ptr;
+  const uint64_t* cpu_req;
+  const int64_t* mem_req;
+  const int64_t* init_ptr;
+  const uint64_t* init_cpu;
+  const int64_t* init_mem;
+  const uint8_t* restartable;
+  const uint64_t* ovh_cpu;
+  const int64_t* ovh_mem;
+};
+
+// Argument checks of the pod model's entry points (host or device pointers alike).
+int check_pods(kcc_ctx* ctx, const PodArgs& a, const uint64_t* pod_cpu, const int64_t* pod_mem) {
+  if (a.n_pods < 0 || a.n_cont < 0 || a.n_init < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (a.n_pods == 0) return KCC_OK;
+  if (!a.pod_ptr || !pod_cpu || !pod_mem) return fail(ctx, KCC_EINVAL, "NULL pod_ptr/output");
+  if (a.n_cont > 0 && (!a.cpu_req || !a.mem_req))
+    return fail(ctx, KCC_EINVAL, "NULL cpu_req/mem_req");
+  if (a.init_ptr && a.n_init > 0 && (!a.init_cpu || !a.init_mem))
+    return fail(ctx, KCC_EINVAL, "NULL init_cpu/init_mem");
   return KCC_OK;
 }
 
-// Stages the pod-level inputs and enqueues the per-pod kernel; pod outputs in q_pcpu/q_pmem.
-int pods_stage_run(kcc_ctx* ctx, Dev& dv, int64_t n_pods, int64_t n_cont, int64_t n_init,
-                   const int64_t* pod_ptr, const uint64_t* cpu_req, const int64_t* mem_req,
-                   const int64_t* init_ptr, const uint64_t* init_cpu, const int64_t* init_mem,
-                   const uint8_t* restartable, const uint64_t* ovh_cpu, const int64_t* ovh_mem) {
-  int rc;
-  if ((rc = h2d(ctx, dv, dv.q_ptr, pod_ptr, n_pods + 1))) return rc;
-  if ((rc = h2d(ctx, dv, dv.cpu, cpu_req, n_cont))) return rc;
-  if ((rc = h2d(ctx, dv, dv.mem, mem_req, n_cont))) return rc;
-  if (init_ptr) {
-    if ((rc = h2d(ctx, dv, dv.q_iptr, init_ptr, n_pods + 1))) return rc;
-    if ((rc = h2d(ctx, dv, dv.q_icpu, init_cpu, n_init))) return rc;
-    if ((rc = h2d(ctx, dv, dv.q_imem, init_mem, n_init))) return rc;
-    if (restartable && (rc = h2d(ctx, dv, dv.q_rst, restartable, n_init))) return rc;
-  }
-  if (ovh_cpu && (rc = h2d(ctx, dv, dv.q_ocpu, ovh_cpu, n_pods))) return rc;
-  if (ovh_mem && (rc = h2d(ctx, dv, dv.q_omem, ovh_mem, n_pods))) return rc;
-  KCC_HIP(ctx, ensure(dv.q_pcpu, 8 * (size_t)n_pods));
-  KCC_HIP(ctx, ensure(dv.q_pmem, 8 * (size_t)n_pods));
-  KCC_HIP(ctx, kcc::launch_pod_requests(
-                   n_pods, n_cont, init_ptr ? n_init : 0, as<int64_t>(dv.q_ptr),
-                   as<uint64_t>(dv.cpu), as<int64_t>(dv.mem),
-                   init_ptr ? as<int64_t>(dv.q_iptr) : nullptr,
-                   init_ptr ? as<uint64_t>(dv.q_icpu) : nullptr,
-                   init_ptr ? as<int64_t>(dv.q_imem) : nullptr,
-                   init_ptr && restartable ? as<uint8_t>(dv.q_rst) : nullptr,
-                   ovh_cpu ? as<uint64_t>(dv.q_ocpu) : nullptr,
-                   ovh_mem ? as<int64_t>(dv.q_omem) : nullptr, as<uint64_t>(dv.q_pcpu),
-                   as<int64_t>(dv.q_pmem), dv.stream));
+// The host forms read the offsets: both CSR arrays are well formed, and there are no init
+// container arrays without init_ptr.
+int check_pods_csr(kcc_ctx* ctx, const PodArgs& a) {
+  const int rc = check_csr(ctx, a.n_pods, a.n_cont, a.pod_ptr);
+  if (rc) return rc;
+  if (a.init_ptr) return check_csr(ctx, a.n_pods, a.n_init, a.init_ptr);
+  if (a.n_init != 0 || a.init_cpu || a.init_mem || a.restartable)
+    return fail(ctx, KCC_EINVAL, "init container arrays without init_ptr");
   return KCC_OK;
+}
+
+int pods_async_dev(kcc_ctx* ctx, const PodArgs& a, uint64_t* pod_cpu, int64_t* pod_mem,
+                   hipStream_t s) {
+  const int rc = check_pods(ctx, a, pod_cpu, pod_mem);
+  if (rc) return rc;
+  KCC_HIP(ctx, kcc::launch_pod_requests(a.n_pods, a.n_cont, a.init_ptr ? a.n_init : 0, a.pod_ptr,
+                                        a.cpu_req, a.mem_req, a.init_ptr, a.init_cpu, a.init_mem,
+                                        a.init_ptr ? a.restartable : nullptr, a.ovh_cpu, a.ovh_mem,
+                                        pod_cpu, pod_mem, s));
+  return KCC_OK;
+}
+
+// Stages the pod-level inputs and enqueues the per-pod kernel into pod_cpu / pod_mem (device).
+int pods_stage_run(kcc_ctx* ctx, Dev& dv, Stage& st, PodArgs a, uint64_t* pod_cpu,
+                   int64_t* pod_mem) {
+  const int64_t n_init = a.init_ptr ? a.n_init : 0;
+  int rc;
+  if ((rc = st.in(a.pod_ptr, csr_len(a.n_pods))) || (rc = st.in(a.cpu_req, a.n_cont)) ||
+      (rc = st.in(a.mem_req, a.n_cont)) || (rc = st.in(a.init_ptr, csr_len(a.n_pods))) ||
+      (rc = st.in(a.init_cpu, n_init)) || (rc = st.in(a.init_mem, n_init)) ||
+      (rc = st.in(a.restartable, n_init)) || (rc = st.in(a.ovh_cpu, a.n_pods)) ||
+      (rc = st.in(a.ovh_mem, a.n_pods)))
+    return rc;
+  return pods_async_dev(ctx, a, pod_cpu, pod_mem, dv.stream);
 }
 
 }  // namespace
@@ -2584,21 +2483,11 @@ int kcc_pod_requests_async(kcc_ctx* ctx, int64_t n_pods, int64_t n_containers, i
                            const int64_t* d_ovh_mem, uint64_t* d_pod_cpu, int64_t* d_pod_mem,
                            void* stream) {
   if (!ctx) return KCC_EINVAL;
-  if (n_pods < 0 || n_containers < 0 || n_init < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  if (n_pods == 0) return KCC_OK;
-  if (!d_pod_ptr || !d_pod_cpu || !d_pod_mem) return fail(ctx, KCC_EINVAL, "NULL pod_ptr/output");
-  if (n_containers > 0 && (!d_cpu_req || !d_mem_req))
-    return fail(ctx, KCC_EINVAL, "NULL cpu_req/mem_req");
-  if (d_init_ptr && n_init > 0 && (!d_init_cpu || !d_init_mem))
-    return fail(ctx, KCC_EINVAL, "NULL init_cpu/init_mem");
-  Dev& dv = ctx->devs[0];
-  KCC_HIP(ctx, hipSetDevice(dv.device));
-  KCC_HIP(ctx, kcc::launch_pod_requests(n_pods, n_containers, d_init_ptr ? n_init : 0, d_pod_ptr,
-                                        d_cpu_req, d_mem_req, d_init_ptr, d_init_cpu, d_init_mem,
-                                        d_init_ptr ? d_restartable : nullptr, d_ovh_cpu,
-                                        d_ovh_mem, d_pod_cpu, d_pod_mem,
-                                        static_cast<hipStream_t>(stream)));
-  return KCC_OK;
+  KCC_HIP(ctx, hipSetDevice(ctx->devs[0].device));
+  return pods_async_dev(ctx,
+                        {n_pods, n_containers, n_init, d_pod_ptr, d_cpu_req, d_mem_req, d_init_ptr,
+                         d_init_cpu, d_init_mem, d_restartable, d_ovh_cpu, d_ovh_mem},
+                        d_pod_cpu, d_pod_mem, static_cast<hipStream_t>(stream));
 }
 
 int kcc_pod_requests(kcc_ctx* ctx, int64_t n_pods, int64_t n_containers, int64_t n_init,
@@ -2607,23 +2496,17 @@ int kcc_pod_requests(kcc_ctx* ctx, int64_t n_pods, int64_t n_containers, int64_t
                      const uint8_t* restartable, const uint64_t* ovh_cpu,
                      const int64_t* ovh_mem, uint64_t* pod_cpu, int64_t* pod_mem) {
   if (!ctx) return KCC_EINVAL;
-  if (n_init < 0) return fail(ctx, KCC_EINVAL, "negative size");
-  int rc = check_pods(ctx, n_pods, n_containers, n_init, pod_ptr, cpu_req, mem_req, init_ptr,
-                      init_cpu, init_mem, restartable);
-  if (rc) return rc;
-  if (n_pods == 0) return KCC_OK;
-  if (!pod_cpu || !pod_mem) return fail(ctx, KCC_EINVAL, "NULL output");
+  const PodArgs a{n_pods, n_containers, n_init, pod_ptr, cpu_req, mem_req, init_ptr,
+                  init_cpu, init_mem, restartable, ovh_cpu, ovh_mem};
+  int rc = check_pods(ctx, a, pod_cpu, pod_mem);
+  if (rc || (rc = check_pods_csr(ctx, a))) return rc;
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = pods_stage_run(ctx, dv, n_pods, n_containers, n_init, pod_ptr, cpu_req, mem_req,
-                           init_ptr, init_cpu, init_mem, restartable, ovh_cpu, ovh_mem)))
+  Stage st(ctx, dv);
+  if ((rc = st.out(pod_cpu, n_pods)) || (rc = st.out(pod_mem, n_pods)) ||
+      (rc = pods_stage_run(ctx, dv, st, a, pod_cpu, pod_mem)))
     return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(pod_cpu, dv.q_pcpu.p, 8 * (size_t)n_pods, hipMemcpyDeviceToHost,
-                              dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(pod_mem, dv.q_pmem.p, 8 * (size_t)n_pods, hipMemcpyDeviceToHost,
-                              dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return KCC_OK;
+  return st.finish();
 }
 
 int kcc_reduce_requests_pods(kcc_ctx* ctx, int64_t n_nodes, int64_t n_pods,
@@ -2634,36 +2517,26 @@ int kcc_reduce_requests_pods(kcc_ctx* ctx, int64_t n_nodes, int64_t n_pods,
                              const uint8_t* restartable, const uint64_t* ovh_cpu,
                              const int64_t* ovh_mem, uint64_t* used_cpu, int64_t* used_mem) {
   if (!ctx) return KCC_EINVAL;
-  if (n_init < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  const PodArgs a{n_pods, n_containers, n_init, pod_ptr, cpu_req, mem_req, init_ptr,
+                  init_cpu, init_mem, restartable, ovh_cpu, ovh_mem};
+  // (the pod sums stay on the device: the node sums stand in for them in the pod checks)
   int rc = check_csr(ctx, n_nodes, n_pods, node_pod_ptr);
-  if (rc) return rc;
-  if ((rc = check_pods(ctx, n_pods, n_containers, n_init, pod_ptr, cpu_req, mem_req, init_ptr,
-                       init_cpu, init_mem, restartable)))
+  if (rc || (rc = check_pods(ctx, a, used_cpu, used_mem)) || (rc = check_pods_csr(ctx, a)))
     return rc;
-  if (n_nodes == 0) return KCC_OK;
-  if (!used_cpu || !used_mem) return fail(ctx, KCC_EINVAL, "NULL output");
+  if (n_nodes > 0 && (!used_cpu || !used_mem)) return fail(ctx, KCC_EINVAL, "NULL output");
   Dev& dv = ctx->devs[0];
   KCC_HIP(ctx, hipSetDevice(dv.device));
-  if ((rc = h2d(ctx, dv, dv.ptr, node_pod_ptr, n_nodes + 1))) return rc;
-  if (n_pods > 0 &&
-      (rc = pods_stage_run(ctx, dv, n_pods, n_containers, n_init, pod_ptr, cpu_req, mem_req,
-                           init_ptr, init_cpu, init_mem, restartable, ovh_cpu, ovh_mem)))
-    return rc;
-  KCC_HIP(ctx, ensure(dv.q_pcpu, 8 * (size_t)(n_pods > 0 ? n_pods : 1)));
-  KCC_HIP(ctx, ensure(dv.q_pmem, 8 * (size_t)(n_pods > 0 ? n_pods : 1)));
-  KCC_HIP(ctx, ensure(dv.used_cpu, 8 * (size_t)n_nodes));
-  KCC_HIP(ctx, ensure(dv.used_mem, 8 * (size_t)n_nodes));
+  Stage st(ctx, dv);
   // the pods of each node are the "containers" of the ordinary segmented reduce
-  rc = reduce_async_dev(ctx, dv, n_nodes, n_pods, as<int64_t>(dv.ptr), as<uint64_t>(dv.q_pcpu),
-                        as<int64_t>(dv.q_pmem), nullptr, nullptr, as<uint64_t>(dv.used_cpu),
-                        as<int64_t>(dv.used_mem), nullptr, nullptr, dv.stream);
-  if (rc) return rc;
-  KCC_HIP(ctx, hipMemcpyAsync(used_cpu, dv.used_cpu.p, 8 * (size_t)n_nodes,
-                              hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipMemcpyAsync(used_mem, dv.used_mem.p, 8 * (size_t)n_nodes,
-                              hipMemcpyDeviceToHost, dv.stream));
-  KCC_HIP(ctx, hipStreamSynchronize(dv.stream));
-  return check_faults(ctx);
+  uint64_t* pod_cpu = nullptr;
+  int64_t* pod_mem = nullptr;
+  if ((rc = st.tmp(pod_cpu, n_pods)) || (rc = st.tmp(pod_mem, n_pods))) return rc;
+  if ((rc = st.in(node_pod_ptr, csr_len(n_nodes))) || (rc = st.out(used_cpu, n_nodes)) ||
+      (rc = st.out(used_mem, n_nodes)) || (rc = pods_stage_run(ctx, dv, st, a, pod_cpu, pod_mem)) ||
+      (rc = reduce_async_dev(ctx, dv, n_nodes, n_pods, node_pod_ptr, pod_cpu, pod_mem, nullptr,
+                             nullptr, used_cpu, used_mem, nullptr, nullptr, dv.stream)))
+    return rc;
+  return st.finish(true);
 }
 
 }  // extern "C"
