@@ -33,6 +33,14 @@
 // the pod-slot clamp — and perNode — the cap), then "Left over <name> : <amount>" per resource
 // (cpu in millicores with an m suffix).  Nothing for a spec on which Go would panic.  -explain
 // with -spreadBy zone is refused: a maxSkew-clipped total is not a sum over rows.
+// -priority p (opt-in): the preemption what-if.  The cluster file's `priority <int>` lines (after
+// a `pod` line, default 0) split the pods in two levels: a pod of priority >= p stays, the rest
+// make way.  Under each spec's result, "With preemption of pods below priority p : <total>, at
+// most <V> pods evicted": the total from kcc_reduce_requests_levels + kcc_fit_levels (L = 2) on
+// the plane without the lower-priority pods, V the pods below p on the rows.  An upper bound:
+// every lower-priority pod yields (no PodDisruptionBudgets, no preemptionPolicy).  It composes
+// with -extRequests, -maxPerNode, -specs and -byPool ("Pool <name> with preemption : <total>"
+// lines after the pools'); with -schedulerRequests, -deploy and -spreadBy zone it is refused.
 #include <array>
 #include <cctype>
 #include <cerrno>
@@ -68,7 +76,7 @@ struct Flags {
       {"gpus", "1"},              {"v", "false"},           {"schedulerRequests", "false"},
       {"byPool", "false"},        {"extRequests", ""},      {"maxPerNode", "0"},
       {"spreadBy", ""},           {"maxSkew", "1"},         {"deploy", ""},
-      {"explain", "false"}};
+      {"explain", "false"},       {"priority", ""}};
 };
 
 // Go flag package syntax: -name=value, -name value, --name=value; bool -v.
@@ -387,6 +395,21 @@ int main(int argc, char** argv) {
 
   // opt-in rollout plan (NOT the reference's arithmetic): its steps as strings
   const bool deployOn = !f.v["deploy"].empty();
+  // opt-in preemption what-if (NOT the reference's arithmetic)
+  const bool prioOn = !f.v["priority"].empty();
+  int64_t prio = 0;
+  if (prioOn) {
+    if (!goAtoiStrict(f.v["priority"], prio)) {
+      std::fprintf(stderr, "invalid value \"%s\" for flag -priority: want an integer priority\n",
+                   f.v["priority"].c_str());
+      return 2;
+    }
+    const char* with = schedReq ? "-schedulerRequests" : deployOn ? "-deploy" : byZone ? "-spreadBy zone" : nullptr;
+    if (with) {
+      std::fprintf(stderr, "-priority cannot be combined with %s: the per-priority sums are the app-container sums of the pods as they stand, and a total clipped by maxSkew has no per-level form\n", with);
+      return 2;
+    }
+  }
   std::vector<Step> plan;
   if (deployOn) {
     if (verbose) {
@@ -739,9 +762,11 @@ int main(int argc, char** argv) {
   std::vector<std::string> pools;
   std::vector<int64_t> ptot;
   std::vector<int32_t> perr;
+  std::vector<int32_t> poolGroup;  // (-priority reads the pools' ids again)
   if (byPool && n > 0) {
     std::map<std::string, int32_t> id;
-    std::vector<int32_t> group((size_t)n);
+    std::vector<int32_t>& group = poolGroup;
+    group.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
       const std::string& name = cl.nodes[(size_t)i].pool;
       auto it = id.find(name);
@@ -806,6 +831,74 @@ int main(int argc, char** argv) {
                          wrows.data(), wpods.data(), left.data());
     if (rc) return fail(ctx, rc);
   }
+  // -priority: two levels of node state in one pass over the containers (the extended
+  // resources' columns two a call, in the cpu_req / mem_req places), then every spec on plane 1;
+  // ltot / lerr [spec], lptot / lperr [pool][spec], evicted = the pods below the priority
+  std::vector<int64_t> ltot((size_t)S, 0), lptot(pools.size() * (size_t)S, 0);
+  std::vector<int32_t> lerr((size_t)S, 0), lperr(pools.size() * (size_t)S, 0);
+  int64_t evicted = 0;
+  if (prioOn && n > 0) {
+    const int64_t P = (int64_t)in.pod_priority.size(), R = ext.R();
+    std::vector<uint8_t> level((size_t)P);
+    for (int64_t p = 0; p < P; ++p) level[(size_t)p] = in.pod_priority[(size_t)p] >= prio ? 1 : 0;
+    std::vector<uint64_t> luc((size_t)(2 * n));
+    std::vector<int64_t> lum((size_t)(2 * n)), lpc((size_t)(2 * n)), lux((size_t)(2 * R * n), 0);
+    rc = kcc_reduce_requests_levels(ctx, n, P, nc, in.lv_node_pod_ptr.data(), in.lv_pod_ptr.data(),
+                                    in.cpu_req.data(), in.mem_req.data(), level.data(), 2,
+                                    luc.data(), lum.data(), lpc.data());
+    if (rc) return fail(ctx, rc);
+    for (int64_t i = 0; i < n; ++i) evicted += lpc[(size_t)i] - lpc[(size_t)(n + i)];
+    for (int64_t r0 = 0; r0 < R; r0 += 2) {
+      std::vector<uint64_t> c0((size_t)nc, 0), o0((size_t)(2 * n));
+      std::vector<int64_t> c1((size_t)nc, 0), o1((size_t)(2 * n)), cnt((size_t)(2 * n));
+      for (int64_t k = 0; k < nc; ++k) {
+        const auto it = ext.creq.find(in.app[(size_t)k]);
+        if (it == ext.creq.end()) continue;
+        c0[(size_t)k] = (uint64_t)it->second[(size_t)r0];
+        if (r0 + 1 < R) c1[(size_t)k] = it->second[(size_t)r0 + 1];
+      }
+      rc = kcc_reduce_requests_levels(ctx, n, P, nc, in.lv_node_pod_ptr.data(), in.lv_pod_ptr.data(),
+                                      c0.data(), c1.data(), level.data(), 2, o0.data(), o1.data(),
+                                      cnt.data());
+      if (rc) return fail(ctx, rc);
+      for (int64_t l = 0; l < 2; ++l)
+        for (int64_t i = 0; i < n; ++i) {
+          lux[(size_t)((l * R + r0) * n + i)] = (int64_t)o0[(size_t)(l * n + i)];
+          if (r0 + 1 < R) lux[(size_t)((l * R + r0 + 1) * n + i)] = o1[(size_t)(l * n + i)];
+        }
+    }
+    const int64_t level_ptr[3] = {0, 0, S};  // every spec at level 1
+    const int64_t* cap = maxPerNode > 0 ? caps.data() : nullptr;
+    rc = kcc_fit_levels(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(), 2,
+                        lpc.data(), luc.data(), lum.data(), R, ext.alloc_x.data(), lux.data(), nullptr,
+                        1, S, sc.data(), sm.data(), ext.spec_x.data(), cap, level_ptr, ltot.data(),
+                        lerr.data());
+    if (rc) return fail(ctx, rc);
+    if (!pools.empty()) {
+      rc = kcc_fit_levels(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(), 2,
+                          lpc.data(), luc.data(), lum.data(), R, ext.alloc_x.data(), lux.data(),
+                          poolGroup.data(), (int64_t)pools.size(), S, sc.data(), sm.data(),
+                          ext.spec_x.data(), cap, level_ptr, lptot.data(), lperr.data());
+      if (rc) return fail(ctx, rc);
+    }
+  }
+  auto printPreempt = [&](size_t s) {
+    if (!prioOn) return;
+    if (lerr[s])
+      std::printf("With preemption of pods below priority %" PRId64 " : panic: runtime error: integer divide by zero\n", prio);
+    else
+      std::printf("With preemption of pods below priority %" PRId64 " : %" PRId64 ", at most %" PRId64
+                  " pods evicted\n", prio, ltot[s], evicted);
+  };
+  auto printPreemptPools = [&](size_t s) {
+    if (!prioOn) return;
+    for (size_t g = 0; g < pools.size(); ++g) {
+      if (lperr[g * specs.size() + s])
+        std::printf("Pool %s with preemption : panic: runtime error: integer divide by zero\n", pools[g].c_str());
+      else
+        std::printf("Pool %s with preemption : %" PRId64 "\n", pools[g].c_str(), lptot[g * specs.size() + s]);
+    }
+  };
   auto printExplain = [&](size_t s) {
     if (!explain || serr[s]) return;
     for (int b = 0; b < KCC_WHY_SLOTS; ++b) {
@@ -843,9 +936,11 @@ int main(int argc, char** argv) {
                   " replicas. Please try again by reducing the number of replicas or/and cpu/memory "
                   "resource requests. Exiting!!\n\n", specs[0].replicas);
     std::printf("%s\n", kRule);
+    printPreempt(0);
     printExplain(0);
     printZones(0);
     printPools(0);
+    printPreemptPools(0);
     return 0;
   }
   // batch: one line per spec
@@ -856,9 +951,11 @@ int main(int argc, char** argv) {
     else
       std::printf("%s %s %s total=%" PRId64 " %s\n", specs[s].cpuStr.c_str(), specs[s].memStr.c_str(),
                   specs[s].repStr.c_str(), totals[s], totals[s] >= specs[s].replicas ? "yes" : "no");
+    printPreempt(s);  // (-priority: this spec's total with preemption under its line)
     printExplain(s);  // (-explain: this spec's reasons and leftovers under its line)
     printZones(s);  // (-spreadBy zone: this spec's zones under its line)
     printPools(s);  // (-byPool: this spec's pools under its line)
+    printPreemptPools(s);
   }
   return 0;
 }

@@ -163,6 +163,10 @@ bool loadCluster(const std::string& path, Cluster& out, std::string& err) {
       if (out.pods.empty()) return bad("overhead before any pod");
       if (!(is >> out.pods.back().overheadCPU >> out.pods.back().overheadMem))
         return bad("overhead <cpuMillis> <memBytes>");
+    } else if (kind == "priority") {
+      if (out.pods.empty()) return bad("priority before any pod");
+      std::string v;
+      if (!(is >> v) || !goAtoi(v, out.pods.back().priority)) return bad("priority <int>");
     } else {
       return bad("unknown record");
     }
@@ -279,7 +283,11 @@ int buildInputs(kcc_ctx* ctx, const Cluster& c, const std::vector<node>& rows, E
     const std::vector<size_t>& pods = it == by_node.end() ? none : it->second;
     for (size_t pi : pods) {
       const Pod& p = c.pods[pi];
-      if (p.getFails) continue;  // NotFound: skipped by the sum (CC:267-268), still counted
+      in.pod_priority.push_back(p.priority);
+      if (p.getFails) {  // NotFound: skipped by the sum (CC:267-268), still counted
+        in.lv_pod_ptr.push_back((int64_t)in.mem_req.size());
+        continue;
+      }
       for (const Container& ct : p.containers) {  // CC:277-293 (app containers only)
         if (ct.init) continue;
         chars += ct.cpuLimit;
@@ -297,12 +305,14 @@ int buildInputs(kcc_ctx* ctx, const Cluster& c, const std::vector<node>& rows, E
         in.init_rst.push_back(ct.restartable ? 1 : 0);
       }
       in.pod_ptr.push_back((int64_t)in.mem_req.size());
+      in.lv_pod_ptr.push_back((int64_t)in.mem_req.size());
       in.init_ptr.push_back((int64_t)in.init_mem.size());
       in.ovh_cpu.push_back(p.overheadCPU);
       in.ovh_mem.push_back(p.overheadMem);
     }
     in.node_ptr.push_back((int64_t)in.mem_req.size());
     in.node_pod_ptr.push_back((int64_t)in.ovh_cpu.size());
+    in.lv_node_pod_ptr.push_back((int64_t)in.pod_priority.size());
     in.alloc_cpu.push_back(r.allocatableCPU);
     in.alloc_mem.push_back(r.allocatableMemory);
     in.alloc_pods.push_back(r.allocatablePods);

@@ -51,6 +51,7 @@ struct Pod {
   bool getFails = false;  // the per-pod Get of CC:264 returns NotFound (CC:267-271)
   uint64_t overheadCPU = 0;  // spec.overhead (millicores, bytes): opt-in model only
   int64_t overheadMem = 0;
+  int64_t priority = 0;  // spec.priority (`priority` line): read only by -priority
 };
 
 struct NodeObj {
@@ -77,6 +78,7 @@ struct Cluster {
 //   container <cpuRequest> <cpuLimit> <memRequestBytes> <memLimitBytes>   (of the last pod)
 //   initcontainer <cpuRequest> <cpuLimit> <memRequestBytes> <memLimitBytes> [always]
 //   overhead <cpuMillis> <memBytes>                                         (of the last pod)
+//   priority <int>                    (of the last pod: spec.priority, default 0; read only by -priority)
 //   request <name> <amount>           (of the last container: its request of an extended resource)
 // (init containers and overhead are read only by -schedulerRequests; the
 // reference's sums ignore them, CC:277; the pool name is read only by -byPool; `resource` and
@@ -115,6 +117,10 @@ struct EngineInputs {
   // the app container behind each CSR entry (cpu_req[k], mem_req[k]): the CLI builds the
   // per-container columns of the extended resources from its `request` lines
   std::vector<const Container*> app;
+  // opt-in preemption what-if (-priority): every counted pod of every row in CSR form, a pod
+  // whose Get fails included (no containers, still counted: CC:106) — lv_pod_ptr indexes
+  // cpu_req / mem_req, plane 0's pod count is pod_count
+  std::vector<int64_t> lv_node_pod_ptr{0}, lv_pod_ptr{0}, pod_priority;
 };
 // The container cpu strings (limits and requests, CC:279-283) are converted on the device
 // in one kcc_parse_cpu_millis batch on `ctx`; each failed string prints

@@ -778,6 +778,95 @@ int kcc_reduce_requests_pods(kcc_ctx* ctx, int64_t n_nodes, int64_t n_pods,
                              const uint8_t* restartable, const uint64_t* ovh_cpu,
                              const int64_t* ovh_mem, uint64_t* used_cpu, int64_t* used_mem);
 
+/* ---------------------------------------------------------------------------
+ * Preemption what-if: per-priority request sums and a levelled fit.  Every fit above treats
+ * the running pods as immovable; the kube-scheduler lets a pod of priority p that does not
+ * fit evict pods of lower priority.  A planner asks both "how many replicas fit as things
+ * stand" and "how many fit if everything below my priority makes way".  OPT-IN, not the
+ * reference's arithmetic; no other entry point changes.
+ *
+ * A level is the rank of a priority class, 0 = lowest; 1 <= n_levels = L <= KCC_LEVELS_MAX.
+ * Plane l of the node state holds the pods a spec of level l cannot evict: those with
+ * pod_level >= l.  Plane 0 is every pod (today's answer); a spec above every pod uses a plane
+ * that holds nothing.  This is an UPPER BOUND: every lower-priority pod yields.
+ * PodDisruptionBudgets, preemptionPolicy: Never and the scheduler's minimal-victim choice are
+ * out of scope.
+ *
+ * kcc_reduce_requests_levels: node_pod_ptr[N+1] (pods grouped by node), pod_ptr[P+1] (each
+ * pod's app containers), cpu_req / mem_req per container as kcc_reduce_requests_pods';
+ * pod_level[P] (uint8; a level >= L counts as L - 1).  Outputs, plane-major [L * N]:
+ *   used_cpu[l*N + i]   the wrapping uint64 sum of cpu_req over the containers of the pods of
+ *                       node i with pod_level >= l
+ *   used_mem[l*N + i]   the same in int64
+ *   pod_count[l*N + i]  the number of such pods (a pod without containers counts: CC:106
+ *                       counts pods)
+ * The app-container sum only (CC:276-294): the opt-in init / sidecar / overhead model above is
+ * not combined here.  Plane 0 of used_* equals kcc_reduce_requests on the flattened CSR bit
+ * for bit, plane 0 of pod_count equals the differences of node_pod_ptr.  Both adds wrap, so an
+ * extended resource needs no entry point of its own: a second call with two extra columns in
+ * the cpu_req / mem_req places gives two planes of used_x.
+ * The host form validates both CSR arrays (offset 0 first, non-decreasing, the size last) and
+ * 1 <= L <= KCC_LEVELS_MAX, else KCC_EINVAL; pods without nodes: KCC_EINVAL.  n_nodes == 0:
+ * KCC_OK, nothing written; n_pods == 0: every output 0.  n_nodes <= 2^31 - 4096.  The async
+ * form takes device pointers and clamps the offsets into range (a malformed CSR gives wrong
+ * sums, never a fault); it only enqueues, allocates nothing and never synchronises.  No kernel
+ * of it waits on another workgroup: it neither sets nor reads the fault words.
+ *
+ * kcc_fit_levels: kcc_fit_capped on the plane of each spec's level.  Node side: alloc_cpu,
+ * alloc_mem, alloc_pods [N]; n_levels; pod_count, used_cpu, used_mem [L * N] (the planes
+ * above); n_ext = R, alloc_x [R * N], used_x [L * R * N] (plane l an ordinary [R * N] block:
+ * a caller without per-level data repeats its block); group, n_groups.  Spec side: n_specs,
+ * spec_cpu, spec_mem, spec_x [R * S], node_cap (nullable) as kcc_fit_capped's, and
+ * level_ptr[L+1], a HOST array in both forms: the specs are given sorted by level, specs
+ * [level_ptr[l], level_ptr[l+1]) have level l.  level_ptr[0] == 0, non-decreasing,
+ * level_ptr[L] == n_specs, else KCC_EINVAL.
+ *   For each level l, columns [level_ptr[l], level_ptr[l+1]) of every group row of totals /
+ *   spec_err [G * S] are exactly kcc_fit_capped's totals and spec_err for those specs on plane
+ *   l's node arrays: the pod-slot clamp uses plane l's pod_count; the divide-by-zero rule,
+ *   empty groups and skipped ids are kcc_fit_capped's.  With L == 1 the call is kcc_fit_capped
+ *   bit for bit, on the same launches.
+ * The intended use: pass a spec twice, at level 0 and at its own level, and read "as things
+ * stand" and "with preemption" side by side.
+ * Size limits and argument errors are kcc_fit_capped's.  n_nodes == 0 or n_specs == 0: KCC_OK,
+ * outputs 0.  Host and async forms as kcc_fit_capped's: the async form only enqueues,
+ * allocates only when a size exceeds every earlier call's, never synchronises and reads no
+ * device value on the host; the number and kind of its launches depend only on (N, G, R, L,
+ * level_ptr), so it can be captured into one graph behind kcc_reduce_requests_levels_async.
+ * No kernel of it waits on another workgroup.
+ * ------------------------------------------------------------------------- */
+#define KCC_LEVELS_MAX 8
+int kcc_reduce_requests_levels(kcc_ctx* ctx, int64_t n_nodes, int64_t n_pods, int64_t n_containers,
+                               const int64_t* node_pod_ptr, const int64_t* pod_ptr,
+                               const uint64_t* cpu_req, const int64_t* mem_req,
+                               const uint8_t* pod_level, int64_t n_levels,
+                               uint64_t* used_cpu /* [L * N] */, int64_t* used_mem /* [L * N] */,
+                               int64_t* pod_count /* [L * N] */);
+int kcc_reduce_requests_levels_async(kcc_ctx* ctx, int64_t n_nodes, int64_t n_pods,
+                                     int64_t n_containers, const int64_t* d_node_pod_ptr,
+                                     const int64_t* d_pod_ptr, const uint64_t* d_cpu_req,
+                                     const int64_t* d_mem_req, const uint8_t* d_pod_level,
+                                     int64_t n_levels, uint64_t* d_used_cpu, int64_t* d_used_mem,
+                                     int64_t* d_pod_count, void* stream);
+int kcc_fit_levels(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                   const int64_t* alloc_mem, const int64_t* alloc_pods, int64_t n_levels,
+                   const int64_t* pod_count /* [L * N] */, const uint64_t* used_cpu /* [L * N] */,
+                   const int64_t* used_mem /* [L * N] */, int64_t n_ext,
+                   const int64_t* alloc_x /* [R * N] */, const int64_t* used_x /* [L * R * N] */,
+                   const int32_t* group /* nullable */, int64_t n_groups, int64_t n_specs,
+                   const uint64_t* spec_cpu, const int64_t* spec_mem,
+                   const int64_t* spec_x /* [R * S] */, const int64_t* node_cap /* [S], nullable */,
+                   const int64_t* level_ptr /* [L + 1], host */, int64_t* totals /* [G * S] */,
+                   int32_t* spec_err /* [G * S] */);
+int kcc_fit_levels_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                         const int64_t* d_alloc_mem, const int64_t* d_alloc_pods, int64_t n_levels,
+                         const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                         const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                         const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                         int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                         const int64_t* d_spec_x, const int64_t* d_node_cap,
+                         const int64_t* h_level_ptr /* [L + 1], host */, int64_t* d_totals,
+                         int32_t* d_spec_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@ KCC_DEPLOY_PACK = 0
 KCC_DEPLOY_SPREAD = 1
 KCC_DEPLOY_TILE = 1024
 KCC_DEPLOY_SCAN_PASS = 256
+KCC_LEVELS_MAX = 8  # include/kcc.h: priority levels of kcc_reduce_requests_levels / kcc_fit_levels
 
 _i64, _i32, _int, _vp, _dbl = C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_double
 
@@ -118,6 +119,13 @@ SIGNATURES = {
     "kcc_pod_requests": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 11),
     "kcc_pod_requests_async": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 12),
     "kcc_reduce_requests_pods": (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 12),
+    "kcc_reduce_requests_levels": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 5 + [_i64] + [_vp] * 3),
+    "kcc_reduce_requests_levels_async": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 5 + [_i64]
+                                         + [_vp] * 4),
+    "kcc_fit_levels": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 3 + [_i64] + [_vp] * 3
+                       + [_i64, _i64] + [_vp] * 7),
+    "kcc_fit_levels_async": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 3 + [_i64]
+                             + [_vp] * 3 + [_i64, _i64] + [_vp] * 8),
 }
 
 # per-string status of kcc_parse_* (include/kcc.h)

@@ -129,6 +129,7 @@ struct Dev {
   DevBuf x_rec;                    // kcc::ExtWork::xrec (the other buffers are GrpWork's)
   DevBuf sp_qmin;                  // kcc_fit_capped: the pre-finalize minima [G S]
   DevBuf ex_free;                  // kcc_fit_explain: the groups' free amounts [(2 + R) G]
+  DevBuf lv_tot, lv_err, lv_x;     // kcc_fit_levels: one level's cells [G S_l], spec_x by level
   DevBuf f_cap, f_present, f_flag;   // kcc::FoldWork (kcc_spread_fold)
   DevBuf dp_a, dp_tsum, dp_toff, dp_flag, dp_st, dp_bins;  // kcc::DeployWork (kcc_deploy)
   DevBuf kb_counts, kb_tot, kb_sr, kb_sv;  // kcc::KeyedWork (bucketed keyed reduce)
@@ -2537,6 +2538,213 @@ int kcc_reduce_requests_pods(kcc_ctx* ctx, int64_t n_nodes, int64_t n_pods,
                              nullptr, used_cpu, used_mem, nullptr, nullptr, dv.stream)))
     return rc;
   return st.finish(true);
+}
+
+}  // extern "C"
+
+
+// ---- preemption what-if: per-priority node state and a levelled fit (kcc_levels.hip) ------
+
+namespace {
+
+struct LevelsReduceArgs {
+  int64_t n_nodes, n_pods, n_cont;
+  const int64_t* node_pod_ptr;
+  const int64_t* pod_ptr;
+  const uint64_t* cpu_req;
+  const int64_t* mem_req;
+  const uint8_t* pod_level;
+  int64_t L;
+  uint64_t* used_cpu;
+  int64_t* used_mem;
+  int64_t* pod_count;
+};
+
+// Argument checks of both reduce forms (host or device pointers alike).
+int check_levels_reduce(kcc_ctx* ctx, const LevelsReduceArgs& a) {
+  if (a.n_nodes < 0 || a.n_pods < 0 || a.n_cont < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (a.L < 1 || a.L > KCC_LEVELS_MAX)
+    return fail(ctx, KCC_EINVAL, "n_levels must be in [1, KCC_LEVELS_MAX]");
+  if (a.n_nodes == 0)
+    return a.n_pods == 0 && a.n_cont == 0 ? KCC_OK : fail(ctx, KCC_EINVAL, "pods without nodes");
+  if (a.n_nodes > kcc::GRP_MAX_NODES) return fail(ctx, KCC_EINVAL, "too many nodes (max 2^31 - 4096)");
+  if (!a.used_cpu || !a.used_mem || !a.pod_count) return fail(ctx, KCC_EINVAL, "NULL output");
+  if (!a.node_pod_ptr) return fail(ctx, KCC_EINVAL, "node_pod_ptr is NULL");
+  if (a.n_pods > 0 && (!a.pod_ptr || !a.pod_level)) return fail(ctx, KCC_EINVAL, "NULL pod_ptr/pod_level");
+  if (a.n_pods == 0 && a.n_cont != 0) return fail(ctx, KCC_EINVAL, "containers without pods");
+  if (a.n_cont > 0 && (!a.cpu_req || !a.mem_req)) return fail(ctx, KCC_EINVAL, "NULL cpu_req/mem_req");
+  return KCC_OK;
+}
+
+int levels_reduce_dev(kcc_ctx* ctx, const LevelsReduceArgs& a, hipStream_t s) {
+  KCC_HIP(ctx, kcc::launch_levels_reduce(a.n_nodes, a.n_pods, a.n_cont, (int)a.L, a.node_pod_ptr,
+                                         a.pod_ptr, a.cpu_req, a.mem_req, a.pod_level, a.used_cpu,
+                                         a.used_mem, a.pod_count, s));
+  return KCC_OK;
+}
+
+// Plane l of the levelled node state: an ordinary FitNodes.
+kcc::FitNodes level_plane(const kcc::FitNodes& nd, int64_t l) {
+  kcc::FitNodes p = nd;
+  if (nd.n > 0) {
+    p.pod_count = nd.pod_count + l * nd.n;
+    p.used_cpu = nd.used_cpu + l * nd.n;
+    p.used_mem = nd.used_mem + l * nd.n;
+    if (nd.R > 0) p.used_x = nd.used_x + l * nd.R * nd.n;
+  }
+  return p;
+}
+
+// Argument checks of both fit forms: kcc_fit_capped's, n_levels and the host array level_ptr.
+int check_fit_levels(kcc_ctx* ctx, const kcc::FitNodes& nd, const kcc::FitSpecs& sp, int64_t L,
+                     const int64_t* level_ptr, const int64_t* totals, const int32_t* spec_err) {
+  if (L < 1 || L > KCC_LEVELS_MAX)
+    return fail(ctx, KCC_EINVAL, "n_levels must be in [1, KCC_LEVELS_MAX]");
+  const int rc = check_cells(ctx, nd, sp, false, totals, spec_err);
+  if (rc) return rc;
+  if (!level_ptr) return fail(ctx, KCC_EINVAL, "level_ptr is NULL");
+  if (level_ptr[0] != 0) return fail(ctx, KCC_EINVAL, "level_ptr[0] != 0");
+  for (int64_t l = 0; l < L; ++l)
+    if (level_ptr[l + 1] < level_ptr[l]) return fail(ctx, KCC_EINVAL, "level_ptr is not non-decreasing");
+  if (level_ptr[L] != sp.S) return fail(ctx, KCC_EINVAL, "level_ptr[n_levels] != n_specs");
+  return KCC_OK;
+}
+
+// Device level (the caller has passed check_fit_levels): one kcc_fit_capped per non-empty
+// level on that level's plane, its cells placed into the level's columns.  The launches
+// depend on (N, G, R, L, level_ptr) alone.
+int fit_levels_dev(kcc_ctx* ctx, Dev& dv, const kcc::FitNodes& nd, const kcc::FitSpecs& sp,
+                   int64_t L, const int64_t* level_ptr, int64_t* totals, int32_t* spec_err,
+                   hipStream_t s) {
+  if (nd.n == 0 || sp.S == 0)  // kcc_fit_capped's degenerate cases
+    return fit_cells_dev(ctx, dv, nd, sp, false, totals, spec_err, nullptr, nullptr, s);
+  int64_t s_max = 0;
+  for (int64_t l = 0; l < L; ++l) {
+    const int64_t sl = level_ptr[l + 1] - level_ptr[l];
+    s_max = sl > s_max ? sl : s_max;
+    if (sl == sp.S)  // one level holds every spec: kcc_fit_capped on its plane, no copy
+      return fit_cells_dev(ctx, dv, level_plane(nd, l), sp, false, totals, spec_err, nullptr,
+                           nullptr, s);
+  }
+  KCC_HIP(ctx, ensure(dv.lv_tot, 8 * (size_t)(nd.G * s_max)));
+  KCC_HIP(ctx, ensure(dv.lv_err, 4 * (size_t)(nd.G * s_max)));
+  if (nd.R > 0) {  // the pair loop strides spec_x by its S: a level's block is [R, S_l]
+    kcc::LevelPtr lp;
+    lp.L = (int)L;
+    for (int64_t l = 0; l <= KCC_LEVELS_MAX; ++l) lp.ptr[l] = level_ptr[l < L ? l : L];
+    KCC_HIP(ctx, ensure(dv.lv_x, 8 * (size_t)(nd.R * sp.S)));
+    KCC_HIP(ctx, kcc::launch_cells_pack_x(nd.R, sp.S, lp, sp.spec_x, as<int64_t>(dv.lv_x), s));
+  }
+  for (int64_t l = 0; l < L; ++l) {
+    const int64_t o = level_ptr[l], sl = level_ptr[l + 1] - o;
+    if (sl == 0) continue;
+    const kcc::FitSpecs spl{sl, sp.spec_cpu + o, sp.spec_mem + o,
+                            nd.R > 0 ? as<int64_t>(dv.lv_x) + nd.R * o : nullptr,
+                            sp.node_cap ? sp.node_cap + o : nullptr};
+    const int rc = fit_cells_dev(ctx, dv, level_plane(nd, l), spl, false, as<int64_t>(dv.lv_tot),
+                                 as<int32_t>(dv.lv_err), nullptr, nullptr, s);
+    if (rc) return rc;
+    KCC_HIP(ctx, kcc::launch_cells_place(nd.G, sp.S, sl, o, as<int64_t>(dv.lv_tot),
+                                         as<int32_t>(dv.lv_err), totals, spec_err, s));
+  }
+  return KCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kcc_reduce_requests_levels_async(kcc_ctx* ctx, int64_t n_nodes, int64_t n_pods,
+                                     int64_t n_containers, const int64_t* d_node_pod_ptr,
+                                     const int64_t* d_pod_ptr, const uint64_t* d_cpu_req,
+                                     const int64_t* d_mem_req, const uint8_t* d_pod_level,
+                                     int64_t n_levels, uint64_t* d_used_cpu, int64_t* d_used_mem,
+                                     int64_t* d_pod_count, void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  const LevelsReduceArgs a{n_nodes, n_pods, n_containers, d_node_pod_ptr, d_pod_ptr, d_cpu_req,
+                           d_mem_req, d_pod_level, n_levels, d_used_cpu, d_used_mem, d_pod_count};
+  const int rc = check_levels_reduce(ctx, a);
+  if (rc || n_nodes == 0) return rc;
+  KCC_HIP(ctx, hipSetDevice(ctx->devs[0].device));
+  return levels_reduce_dev(ctx, a, static_cast<hipStream_t>(stream));
+}
+
+int kcc_reduce_requests_levels(kcc_ctx* ctx, int64_t n_nodes, int64_t n_pods, int64_t n_containers,
+                               const int64_t* node_pod_ptr, const int64_t* pod_ptr,
+                               const uint64_t* cpu_req, const int64_t* mem_req,
+                               const uint8_t* pod_level, int64_t n_levels, uint64_t* used_cpu,
+                               int64_t* used_mem, int64_t* pod_count) {
+  if (!ctx) return KCC_EINVAL;
+  LevelsReduceArgs a{n_nodes, n_pods, n_containers, node_pod_ptr, pod_ptr, cpu_req,
+                     mem_req, pod_level, n_levels, used_cpu, used_mem, pod_count};
+  int rc = check_levels_reduce(ctx, a);
+  if (rc || n_nodes == 0) return rc;
+  // the host form reads the offsets: both CSR arrays are well formed
+  if ((rc = check_csr(ctx, n_nodes, n_pods, node_pod_ptr)) ||
+      (rc = check_csr(ctx, n_pods, n_containers, pod_ptr)))
+    return rc;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  Stage st(ctx, dv);
+  const int64_t planes = n_levels * n_nodes;
+  if ((rc = st.in(a.node_pod_ptr, csr_len(n_nodes))) || (rc = st.in(a.pod_ptr, csr_len(n_pods))) ||
+      (rc = st.in(a.cpu_req, n_containers)) || (rc = st.in(a.mem_req, n_containers)) ||
+      (rc = st.in(a.pod_level, n_pods)) || (rc = st.out(a.used_cpu, planes)) ||
+      (rc = st.out(a.used_mem, planes)) || (rc = st.out(a.pod_count, planes)) ||
+      (rc = levels_reduce_dev(ctx, a, dv.stream)))
+    return rc;
+  return st.finish();
+}
+
+int kcc_fit_levels_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                         const int64_t* d_alloc_mem, const int64_t* d_alloc_pods, int64_t n_levels,
+                         const int64_t* d_pod_count, const uint64_t* d_used_cpu,
+                         const int64_t* d_used_mem, int64_t n_ext, const int64_t* d_alloc_x,
+                         const int64_t* d_used_x, const int32_t* d_group, int64_t n_groups,
+                         int64_t n_specs, const uint64_t* d_spec_cpu, const int64_t* d_spec_mem,
+                         const int64_t* d_spec_x, const int64_t* d_node_cap,
+                         const int64_t* h_level_ptr, int64_t* d_totals, int32_t* d_spec_err,
+                         void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  const kcc::FitNodes nd{n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count, d_used_cpu,
+                         d_used_mem, n_ext, d_alloc_x, d_used_x, d_group, n_groups};
+  const kcc::FitSpecs sp{n_specs, d_spec_cpu, d_spec_mem, d_spec_x, d_node_cap};
+  const int rc = check_fit_levels(ctx, nd, sp, n_levels, h_level_ptr, d_totals, d_spec_err);
+  if (rc) return rc;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  return fit_levels_dev(ctx, dv, nd, sp, n_levels, h_level_ptr, d_totals, d_spec_err,
+                        static_cast<hipStream_t>(stream));
+}
+
+int kcc_fit_levels(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                   const int64_t* alloc_mem, const int64_t* alloc_pods, int64_t n_levels,
+                   const int64_t* pod_count, const uint64_t* used_cpu, const int64_t* used_mem,
+                   int64_t n_ext, const int64_t* alloc_x, const int64_t* used_x,
+                   const int32_t* group, int64_t n_groups, int64_t n_specs,
+                   const uint64_t* spec_cpu, const int64_t* spec_mem, const int64_t* spec_x,
+                   const int64_t* node_cap, const int64_t* level_ptr, int64_t* totals,
+                   int32_t* spec_err) {
+  if (!ctx) return KCC_EINVAL;
+  kcc::FitNodes nd{n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                   n_ext, alloc_x, used_x, group, n_groups};
+  kcc::FitSpecs sp{n_specs, spec_cpu, spec_mem, spec_x, node_cap};
+  int rc = check_fit_levels(ctx, nd, sp, n_levels, level_ptr, totals, spec_err);
+  if (rc) return rc;
+  const int64_t n = n_nodes, S = n_specs, cells = n_groups * n_specs, ln = n_levels * n_nodes;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  Stage st(ctx, dv);
+  if ((rc = st.in(nd.alloc_cpu, n)) || (rc = st.in(nd.alloc_mem, n)) ||
+      (rc = st.in(nd.alloc_pods, n)) || (rc = st.in(nd.pod_count, ln)) ||
+      (rc = st.in(nd.used_cpu, ln)) || (rc = st.in(nd.used_mem, ln)) ||
+      (rc = st.in(nd.alloc_x, nd.R * n)) || (rc = st.in(nd.used_x, nd.R * ln)) ||
+      (rc = st.in(nd.group, n)) || (rc = st.in(sp.spec_cpu, S)) || (rc = st.in(sp.spec_mem, S)) ||
+      (rc = st.in(sp.spec_x, nd.R * S)) || (rc = st.in(sp.node_cap, S)) ||
+      (rc = st.out(totals, cells)) || (rc = st.out(spec_err, cells)) ||
+      (rc = fit_levels_dev(ctx, dv, nd, sp, n_levels, level_ptr, totals, spec_err, dv.stream)))
+    return rc;
+  return st.finish();
 }
 
 }  // extern "C"

@@ -999,4 +999,30 @@ hipError_t launch_pod_requests(int64_t n_pods, int64_t n_cont, int64_t n_init,
                                const int64_t* ovh_mem, uint64_t* pod_cpu, int64_t* pod_mem,
                                hipStream_t s);
 
+// ---- preemption what-if (kcc_levels.hip) ---------------------------
+constexpr int LEVELS_MAX = 8;     // include/kcc.h KCC_LEVELS_MAX
+constexpr int LV_WG = 256;        // pods per tile: one lane each
+constexpr int LV_TILES_MAX = 8;   // consecutive tiles of one workgroup, at most
+constexpr int LV_MIN_GRID = 256;  // workgroups the grid keeps before a workgroup takes more tiles
+// kcc_reduce_requests_levels: used_cpu / used_mem / pod_count [L, N], plane l the pods with
+// min(pod_level, L - 1) >= l.  The three outputs are zeroed on s first; offsets are clamped.
+// N <= 0: nothing; n_pods == 0: the zeroes.  1 <= L <= LEVELS_MAX.
+hipError_t launch_levels_reduce(int64_t N, int64_t n_pods, int64_t n_cont, int L,
+                                const int64_t* node_pod_ptr, const int64_t* pod_ptr,
+                                const uint64_t* cpu_req, const int64_t* mem_req,
+                                const uint8_t* pod_level, uint64_t* used_cpu, int64_t* used_mem,
+                                int64_t* pod_count, hipStream_t s);
+// kcc_fit_levels: the specs' level offsets (host values, passed to the kernels by value).
+struct LevelPtr {
+  int L;
+  int64_t ptr[LEVELS_MAX + 1];
+};
+// spec_x [R, S] to one [R, S_l] block per level, level l's at packed + R * lp.ptr[l].
+hipError_t launch_cells_pack_x(int64_t R, int64_t S, const LevelPtr& lp, const int64_t* spec_x,
+                               int64_t* packed, hipStream_t s);
+// cell_tot / cell_err [G, Sl] to columns col0 .. col0 + Sl of totals / spec_err [G, S].
+hipError_t launch_cells_place(int64_t G, int64_t S, int64_t Sl, int64_t col0,
+                              const int64_t* cell_tot, const int32_t* cell_err, int64_t* totals,
+                              int32_t* spec_err, hipStream_t s);
+
 }  // namespace kcc

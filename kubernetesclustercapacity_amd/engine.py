@@ -711,6 +711,120 @@ class CapacityEngine:
                                                        _p(um)))
         return uc, um
 
+    # -- preemption what-if (opt-in; include/kcc.h) ------------------
+    def reduce_requests_levels(self, node_pod_ptr, pod_ptr, cpu_req, mem_req, pod_level,
+                               n_levels):
+        """Per-node sums per priority level in one pass over the containers (pods grouped by
+        node, CSR node_pod_ptr[N+1]; containers by pod, pod_ptr[P+1]; pod_level uint8 [P], a
+        level >= n_levels counts as n_levels - 1).  Plane l holds the pods a spec of level l
+        cannot evict (pod_level >= l); plane 0 is every pod.  An upper bound: every
+        lower-priority pod yields (no PodDisruptionBudgets, no preemptionPolicy).  Opt-in, not
+        the reference's arithmetic.  Returns (used_cpu uint64, used_mem int64, pod_count int64),
+        each [n_levels, N]."""
+        npp, pp = _arr(node_pod_ptr, np.int64), _arr(pod_ptr, np.int64)
+        if npp.size < 1 or pp.size < 1:
+            raise ValueError("node_pod_ptr / pod_ptr need n + 1 entries")
+        n, P = npp.size - 1, pp.size - 1
+        cr, mr = _arr(cpu_req, np.uint64), _arr(mem_req, np.int64)
+        lv = _arr(pod_level, np.uint8)
+        if cr.size != mr.size:
+            raise ValueError("container arrays differ in length")
+        if lv.size != P:
+            raise ValueError("pod_level needs one entry per pod")
+        L = int(n_levels)
+        shape = (max(L, 0), n)
+        uc, um, pc = np.zeros(shape, np.uint64), np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+        self._check(self._lib.kcc_reduce_requests_levels(
+            self._h, n, P, cr.size, _p(npp), _p(pp), _p(cr), _p(mr), _p(lv), L, _p(uc), _p(um),
+            _p(pc)))
+        return uc, um, pc
+
+    def reduce_requests_levels_async(self, node_pod_ptr, pod_ptr, cpu_req, mem_req, pod_level,
+                                     n_levels, used_cpu, used_mem, pod_count, stream=None):
+        """Device form of reduce_requests_levels (torch tensors on the engine's device; the
+        outputs hold n_levels * N elements, plane-major).  Offsets are clamped on the device."""
+        self._check(self._lib.kcc_reduce_requests_levels_async(
+            self._h, node_pod_ptr.numel() - 1, pod_ptr.numel() - 1,
+            0 if cpu_req is None else cpu_req.numel(), _dp(node_pod_ptr), _dp(pod_ptr),
+            _dp(cpu_req), _dp(mem_req), _dp(pod_level), int(n_levels), _dp(used_cpu),
+            _dp(used_mem), _dp(pod_count), _stream(stream)))
+
+    def fit_levels(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem,
+                   alloc_x, used_x, spec_cpu, spec_mem, spec_x, spec_level=None, group=None,
+                   n_groups=1, node_cap=None, level_ptr=None):
+        """fit_capped with node state that depends on the spec's priority level: pod_count,
+        used_cpu and used_mem are [L, N] planes (reduce_requests_levels'), used_x [L, R, N] or
+        one [R, N] block for every level, and spec s is fitted on plane spec_level[s].  The
+        specs come in any order: they are sorted stably by level for the call and the outputs
+        returned in the caller's order (level_ptr [L + 1] instead of spec_level: the specs are
+        sorted already).  The intended use passes a spec twice, at level 0 and at its own
+        level: "as things stand" beside "with preemption".  Returns (totals int64, err int32),
+        [S] without group ids and [n_groups, S] with them."""
+        pc, uc, um = _arr(pod_count, np.int64), _arr(used_cpu, np.uint64), _arr(used_mem, np.int64)
+        if pc.ndim != 2 or uc.shape != pc.shape or um.shape != pc.shape:
+            raise ValueError("pod_count, used_cpu and used_mem must all be [L, N]")
+        L, n = pc.shape
+        sc = _arr(spec_cpu, np.uint64)
+        S = sc.size
+        if (spec_level is None) == (level_ptr is None):
+            raise ValueError("pass spec_level or level_ptr")
+        if level_ptr is None:
+            lv = _arr(spec_level, np.int64)
+            if lv.shape != (S,) or (S and (lv.min() < 0 or lv.max() >= L)):
+                raise ValueError("spec_level must be [S] with values in [0, L)")
+            order = np.argsort(lv, kind="stable")
+            lp = np.concatenate([[0], np.cumsum(np.bincount(lv, minlength=L))]).astype(np.int64)
+        else:
+            order = np.arange(S)
+            lp = _arr(level_ptr, np.int64)
+            if lp.shape != (L + 1,):
+                raise ValueError("level_ptr must be [L + 1]")
+        ux = None if used_x is None else _arr(used_x, np.int64)
+        if ux is not None and ux.ndim == 2:
+            ux = np.ascontiguousarray(np.broadcast_to(ux, (L,) + ux.shape))
+        if ux is not None and (ux.ndim != 3 or ux.shape[0] != L):
+            raise ValueError("used_x must be [R, N] or [L, R, N]")
+        sx = None if spec_x is None else _arr(spec_x, np.int64)
+        a, R, ax, _, group, G, sc, sm, sx, totals, err = self._cell_args(
+            (alloc_cpu, alloc_mem, alloc_pods, pc[0] if L else np.zeros(n), uc[0] if L else np.zeros(n),
+             um[0] if L else np.zeros(n)), sc[order], _arr(spec_mem, np.int64)[order], group,
+            n_groups, alloc_x, None if ux is None else ux[0],
+            None if sx is None else (sx[:, order] if sx.ndim == 2 else sx))
+        cap = None if node_cap is None else _arr(node_cap, np.int64)
+        if cap is not None and cap.shape != (S,):
+            raise ValueError("node_cap must be [S]")
+        cap = None if cap is None else np.ascontiguousarray(cap[order])
+        if ux is None:
+            ux = np.zeros((L, 0, n), np.int64)
+        self._check(self._lib.kcc_fit_levels(
+            self._h, n, _p(a[0]), _p(a[1]), _p(a[2]), L, _p(pc), _p(uc), _p(um), R, _p(ax), _p(ux),
+            _p(group), G, S, _p(sc), _p(sm), _p(sx), _p(cap), _p(lp), _p(totals), _p(err)))
+        back_t, back_e = np.empty_like(totals), np.empty_like(err)
+        back_t[:, order] = totals
+        back_e[:, order] = err
+        if group is None:
+            return back_t[0], back_e[0]
+        return back_t, back_e
+
+    def fit_levels_async(self, alloc_cpu, alloc_mem, alloc_pods, n_levels, pod_count, used_cpu,
+                         used_mem, n_ext, alloc_x, used_x, group, n_groups, spec_cpu, spec_mem,
+                         spec_x, node_cap, level_ptr, totals, spec_err, stream=None):
+        """Device form of fit_levels (torch tensors on the engine's device: pod_count / used_cpu
+        / used_mem of n_levels * N elements, used_x of n_levels * n_ext * N, the rest as
+        fit_capped_async's).  level_ptr is a HOST sequence of n_levels + 1 offsets into the
+        specs, which are sorted by level.  The arguments go to the C-ABI as they are (None:
+        NULL), which validates them."""
+        n = 0 if alloc_cpu is None else alloc_cpu.numel()
+        s = 0 if spec_cpu is None else spec_cpu.numel()
+        lp = None if level_ptr is None else _arr(level_ptr, np.int64)
+        if lp is not None and lp.size != int(n_levels) + 1 and 1 <= int(n_levels) <= _lib.KCC_LEVELS_MAX:
+            raise ValueError("level_ptr must hold n_levels + 1 offsets")
+        self._check(self._lib.kcc_fit_levels_async(
+            self._h, n, _dp(alloc_cpu), _dp(alloc_mem), _dp(alloc_pods), int(n_levels),
+            _dp(pod_count), _dp(used_cpu), _dp(used_mem), int(n_ext), _dp(alloc_x), _dp(used_x),
+            _dp(group), int(n_groups), s, _dp(spec_cpu), _dp(spec_mem), _dp(spec_x),
+            _dp(node_cap), _p(lp), _dp(totals), _dp(spec_err), _stream(stream)))
+
     def quantity_value(self, strings):
         """resource.Quantity.Value() of ParseQuantity (CC:285-286, parity unpinned: see
         include/kcc.h) over a batch.  Returns (int64 values, int8 status)."""
