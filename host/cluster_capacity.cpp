@@ -41,6 +41,20 @@
 // every lower-priority pod yields (no PodDisruptionBudgets, no preemptionPolicy).  It composes
 // with -extRequests, -maxPerNode, -specs and -byPool ("Pool <name> with preemption : <total>"
 // lines after the pools'); with -schedulerRequests, -deploy and -spreadBy zone it is refused.
+// -drain pool=<name> | zone=<name> | node=<a,b,...> (opt-in): the drain what-if.  The named
+// nodes' rows go away; their pods (a pod's request is the sum of its app containers; a pod with
+// a `daemon` line in the cluster file goes away with its node) are placed on the other nodes by
+// kcc_drain, one step per distinct request shape, biggest first, under -drainPolicy pack|spread
+// (default spread, the scheduler's least-allocated habit).  After the echo line (CC:85):
+// "Drained <n> nodes : <E> pods evicted, <placed> placed, <U> not placed (<D> shapes)", or
+// "..., shapes exceed <max>: none placed"; a shape with a zero cpu or memory request that meets
+// free room is not placed and gets a "Drain shape <cpu>m <mem> : ..." line.  Every later number
+// comes from the drained state.  A placement the scheduler could make, not the one it will:
+// the evicted pods' selectors, affinities, PodDisruptionBudgets and priorities are not read.
+// It composes with -specs, -byPool, -extRequests, -maxPerNode, -spreadBy zone and -explain;
+// with -deploy, -priority, -schedulerRequests and -v it is refused.  A name no node carries is
+// an error (exit status 1).  An unhealthy node among the named ones is not drained and not
+// counted: its row is a zero row already (CC:221-226) and the reference lists no pods for it.
 #include <array>
 #include <cctype>
 #include <cerrno>
@@ -76,7 +90,8 @@ struct Flags {
       {"gpus", "1"},              {"v", "false"},           {"schedulerRequests", "false"},
       {"byPool", "false"},        {"extRequests", ""},      {"maxPerNode", "0"},
       {"spreadBy", ""},           {"maxSkew", "1"},         {"deploy", ""},
-      {"explain", "false"},       {"priority", ""}};
+      {"explain", "false"},       {"priority", ""},         {"drain", ""},
+      {"drainPolicy", "spread"}};
 };
 
 // Go flag package syntax: -name=value, -name value, --name=value; bool -v.
@@ -410,6 +425,47 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  // opt-in drain what-if (NOT the reference's arithmetic): which rows go away, and the policy
+  // under which their pods are placed on the rest
+  const bool drainOn = !f.v["drain"].empty();
+  std::string drainKind;
+  std::vector<std::string> drainNames;
+  int drainPolicy = KCC_DEPLOY_SPREAD;
+  if (f.v["drainPolicy"] == "pack") {
+    drainPolicy = KCC_DEPLOY_PACK;
+  } else if (f.v["drainPolicy"] != "spread") {
+    std::fprintf(stderr, "invalid value \"%s\" for flag -drainPolicy: want pack or spread\n",
+                 f.v["drainPolicy"].c_str());
+    return 2;
+  }
+  if (drainOn) {
+    const std::string& d = f.v["drain"];
+    const size_t eq = d.find('=');
+    drainKind = eq == std::string::npos ? "" : d.substr(0, eq);
+    if ((drainKind != "pool" && drainKind != "zone" && drainKind != "node") || eq + 1 == d.size()) {
+      std::fprintf(stderr, "invalid value \"%s\" for flag -drain: want pool=<name>, zone=<name> or node=<a,b,...>\n",
+                   d.c_str());
+      return 2;
+    }
+    if (drainKind == "node") {
+      std::istringstream is(d.substr(eq + 1));
+      std::string item;
+      while (std::getline(is, item, ','))
+        if (!item.empty()) drainNames.push_back(item);
+    } else {
+      drainNames.push_back(d.substr(eq + 1));
+    }
+    if (drainNames.empty()) {  // node=, : no name at all
+      std::fprintf(stderr, "invalid value \"%s\" for flag -drain: want pool=<name>, zone=<name> or node=<a,b,...>\n",
+                   d.c_str());
+      return 2;
+    }
+    const char* with = deployOn ? "-deploy" : prioOn ? "-priority" : schedReq ? "-schedulerRequests" : verbose ? "-v" : nullptr;
+    if (with) {
+      std::fprintf(stderr, "-drain cannot be combined with %s: the drain places the evicted pods' app-container sums on the per-node sums as they stand, in one pass of its own\n", with);
+      return 2;
+    }
+  }
   std::vector<Step> plan;
   if (deployOn) {
     if (verbose) {
@@ -567,7 +623,7 @@ int main(int argc, char** argv) {
   // -deploy: the plan's steps on the per-node sums and pod counts, in file order; every fit
   // below then reads the updated state (suc / sum_ / euc / eum, in.pod_count, ext.used_x) as
   // the -schedulerRequests path reads its explicit sums
-  const bool explicitSums = schedReq || deployOn;
+  const bool explicitSums = schedReq || deployOn || drainOn;
   if (deployOn) {
     if (!schedReq && !useExt) {  // the per-node request sums (CC:290-293)
       euc.assign((size_t)n, 0);
@@ -609,6 +665,81 @@ int main(int argc, char** argv) {
                     s.memStr.c_str(), s.repStr.c_str(), placed[k], used[k]);
       }
       k0 = k1;
+    }
+    suc = euc;
+    sum_ = eum;
+  }
+
+  // -drain: the rows of the named pool, zone or nodes go away.  Row i is node i's; a pod's
+  // request is the sum of its app containers (CC:276-294), a `daemon` pod goes away with its
+  // node.  kcc_drain leaves the drained rows full and places the evicted pods on the rest;
+  // every fit below reads the updated state, as after -deploy.
+  if (drainOn) {
+    std::vector<uint8_t> mask((size_t)n, 0);
+    for (const std::string& want : drainNames) {
+      bool found = false;
+      for (int64_t i = 0; i < n; ++i) {
+        const NodeObj& nd = cl.nodes[(size_t)i];
+        const std::string& have = drainKind == "pool" ? nd.pool : drainKind == "zone" ? nd.zone : nd.name;
+        if (have == want) {
+          // an unhealthy node's row is a zero row already (CC:221-226) and the reference lists
+          // no pods for it: the name is known, but there is nothing to drain and it is not counted
+          if (!rows[(size_t)i].name.empty()) mask[(size_t)i] = 1;
+          found = true;
+        }
+      }
+      if (!found) {
+        std::fprintf(stderr, "-drain: no node with %s %s in %s\n", drainKind == "node" ? "name" : drainKind.c_str(),
+                     want.c_str(), path.c_str());
+        kcc_destroy(ctx);
+        return 1;
+      }
+    }
+    if (!useExt) {  // the per-node request sums (CC:290-293)
+      euc.assign((size_t)n, 0);
+      eum.assign((size_t)n, 0);
+      rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(), in.mem_req.data(),
+                               nullptr, nullptr, euc.data(), eum.data(), nullptr, nullptr);
+      if (rc) return fail(ctx, rc);
+    }
+    const size_t P = in.pod_daemon.size(), R = (size_t)ext.R();
+    std::vector<uint64_t> pcpu(P, 0);
+    std::vector<int64_t> pmem(P, 0), px(R * P, 0);
+    std::vector<uint8_t> movable(P);
+    for (size_t p = 0; p < P; ++p) {
+      movable[p] = in.pod_daemon[p] ? 0 : 1;
+      for (int64_t k = in.lv_pod_ptr[p]; k < in.lv_pod_ptr[p + 1]; ++k) {
+        pcpu[p] += in.cpu_req[(size_t)k];
+        pmem[p] = (int64_t)((uint64_t)pmem[p] + (uint64_t)in.mem_req[(size_t)k]);
+        const auto it = ext.creq.find(in.app[(size_t)k]);
+        if (it == ext.creq.end()) continue;
+        for (size_t r = 0; r < R; ++r)
+          px[r * P + p] = (int64_t)((uint64_t)px[r * P + p] + (uint64_t)it->second[r]);
+      }
+    }
+    const int64_t M = KCC_DRAIN_MAX_SHAPES;
+    int64_t summary[KCC_DRAIN_SUMMARY] = {0, 0, 0, 0};
+    std::vector<uint64_t> shc((size_t)M);
+    std::vector<int64_t> shm((size_t)M), shx(R * (size_t)M), shn((size_t)M), shp((size_t)M), shu((size_t)M);
+    std::vector<int32_t> she((size_t)M);
+    rc = kcc_drain(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(), ext.R(),
+                   ext.alloc_x.data(), in.pod_count.data(), euc.data(), eum.data(), ext.used_x.data(),
+                   mask.data(), (int64_t)P, in.lv_node_pod_ptr.data(), pcpu.data(), pmem.data(),
+                   px.data(), movable.data(), drainPolicy, M, summary, shc.data(), shm.data(),
+                   shx.data(), shn.data(), shp.data(), shu.data(), she.data());
+    if (rc) return fail(ctx, rc);
+    if (summary[2] < 0) {
+      std::printf("Drained %" PRId64 " nodes : %" PRId64 " pods evicted, shapes exceed %" PRId64
+                  ": none placed\n", summary[0], summary[1], M);
+    } else {
+      std::printf("Drained %" PRId64 " nodes : %" PRId64 " pods evicted, %" PRId64 " placed, %" PRId64
+                  " not placed (%" PRId64 " shapes)\n", summary[0], summary[1], summary[3],
+                  summary[1] - summary[3], summary[2]);
+      for (int64_t j = 0; j < summary[2]; ++j)
+        if (she[(size_t)j])
+          std::printf("Drain shape %" PRIu64 "m %" PRId64 " : %" PRId64 " pods not placed, a zero request "
+                      "(panic: runtime error: integer divide by zero)\n", shc[(size_t)j], shm[(size_t)j],
+                      shn[(size_t)j]);
     }
     suc = euc;
     sum_ = eum;

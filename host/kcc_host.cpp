@@ -167,6 +167,9 @@ bool loadCluster(const std::string& path, Cluster& out, std::string& err) {
       if (out.pods.empty()) return bad("priority before any pod");
       std::string v;
       if (!(is >> v) || !goAtoi(v, out.pods.back().priority)) return bad("priority <int>");
+    } else if (kind == "daemon") {
+      if (out.pods.empty()) return bad("daemon before any pod");
+      out.pods.back().daemon = true;
     } else {
       return bad("unknown record");
     }
@@ -284,6 +287,7 @@ int buildInputs(kcc_ctx* ctx, const Cluster& c, const std::vector<node>& rows, E
     for (size_t pi : pods) {
       const Pod& p = c.pods[pi];
       in.pod_priority.push_back(p.priority);
+      in.pod_daemon.push_back(p.daemon ? 1 : 0);
       if (p.getFails) {  // NotFound: skipped by the sum (CC:267-268), still counted
         in.lv_pod_ptr.push_back((int64_t)in.mem_req.size());
         continue;

@@ -52,6 +52,7 @@ struct Pod {
   uint64_t overheadCPU = 0;  // spec.overhead (millicores, bytes): opt-in model only
   int64_t overheadMem = 0;
   int64_t priority = 0;  // spec.priority (`priority` line): read only by -priority
+  bool daemon = false;   // `daemon` line: bound to its node (DaemonSet, static pod); read only by -drain
 };
 
 struct NodeObj {
@@ -79,6 +80,7 @@ struct Cluster {
 //   initcontainer <cpuRequest> <cpuLimit> <memRequestBytes> <memLimitBytes> [always]
 //   overhead <cpuMillis> <memBytes>                                         (of the last pod)
 //   priority <int>                    (of the last pod: spec.priority, default 0; read only by -priority)
+//   daemon                            (of the last pod: it cannot move to another node; read only by -drain)
 //   request <name> <amount>           (of the last container: its request of an extended resource)
 // (init containers and overhead are read only by -schedulerRequests; the
 // reference's sums ignore them, CC:277; the pool name is read only by -byPool; `resource` and
@@ -121,6 +123,7 @@ struct EngineInputs {
   // whose Get fails included (no containers, still counted: CC:106) — lv_pod_ptr indexes
   // cpu_req / mem_req, plane 0's pod count is pod_count
   std::vector<int64_t> lv_node_pod_ptr{0}, lv_pod_ptr{0}, pod_priority;
+  std::vector<uint8_t> pod_daemon;  // per counted pod (-drain: a daemon pod goes away with its node)
 };
 // The container cpu strings (limits and requests, CC:279-283) are converted on the device
 // in one kcc_parse_cpu_millis batch on `ctx`; each failed string prints

@@ -867,6 +867,94 @@ int kcc_fit_levels_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_
                          const int64_t* h_level_ptr /* [L + 1], host */, int64_t* d_totals,
                          int32_t* d_spec_err, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Drain what-if: the pods of drained nodes re-placed before the fit.  Every call above treats
+ * the node set as fixed.  "I cordon and drain this pool, or zone b goes dark: do the pods that
+ * ran there still fit on the rest, and what is left for my spec afterwards?" takes rows away:
+ * kcc_drain leaves the drained rows full, turns the pods that ran on them into a kcc_deploy
+ * plan — one step per distinct request shape, big shapes first — places it on the surviving
+ * rows and leaves the node state (on the device, in the async form) for the fit that follows.
+ * OPT-IN, not the reference's arithmetic; no other entry point changes.
+ * It is A placement the scheduler could make, not THE one it will make: the evicted pods' own
+ * selectors, affinities, PodDisruptionBudgets and priorities are out of scope.
+ *
+ *   Node arrays as kcc_deploy's: alloc_cpu, alloc_mem, alloc_pods, n_ext = R, alloc_x [R * N].
+ *   State, updated in place: pod_count [N], used_cpu [N], used_mem [N], used_x [R * N].
+ *   drain [N] (uint8): row i is drained iff drain[i] != 0.
+ *   The pods, grouped by node: node_pod_ptr [N + 1] (row i runs pods [node_pod_ptr[i],
+ *     node_pod_ptr[i+1])), pod_cpu [P], pod_mem [P], pod_x [R * P] (nullable: zeros),
+ *     pod_movable [P] (uint8, nullable: every pod movable).
+ *   policy: KCC_DEPLOY_PACK or KCC_DEPLOY_SPREAD.  1 <= max_shapes = M <= KCC_DRAIN_MAX_SHAPES.
+ *   Outputs: summary [KCC_DRAIN_SUMMARY]; shape_cpu, shape_mem, shape_count, shape_placed,
+ *     shape_nodes (int64 but shape_cpu, uint64) and shape_err (int32), each [M]; shape_x [R * M].
+ *
+ *   1. The evicted pods are the pods p of the drained rows with pod_movable == NULL or
+ *      pod_movable[p] != 0.  An unmovable pod (DaemonSet, static pod) goes away with its node.
+ *      summary[0] = the drained rows, summary[1] = the evicted pods.
+ *   2. A drained row is left full: used_cpu[i] = alloc_cpu[i], used_mem[i] = alloc_mem[i],
+ *      used_x[r][i] = alloc_x[r][i] for every r, pod_count[i] = alloc_pods[i].  Every fit of
+ *      this library then gives the row exactly 0 for every spec and never raises the
+ *      divide-by-zero flag on it (no free CPU or memory: qc = qm = qx = 0; the clamp, if it
+ *      fires, gives alloc_pods - pod_count = 0), and a deploy step places nothing on it: the
+ *      state alone carries the drain into whatever call follows, the alloc_* arrays stay as
+ *      they are.  kcc_fit_explain counts such a row under KCC_WHY_CPU with 0 replicas and 0
+ *      left over.
+ *   3. The shape of pod p is (pod_cpu[p], pod_mem[p], pod_x[0][p], ..., pod_x[R-1][p]); two pods
+ *      share a shape iff all 2 + R words are equal.  D = the distinct shapes among the evicted
+ *      pods, ordered DESCENDING, lexicographically, cpu compared as uint64 and every other
+ *      word as int64 (big pods first: first-fit decreasing).  shape_cpu[j], shape_mem[j],
+ *      shape_x[r * M + j] are shape j's words, shape_count[j] the evicted pods of that shape.
+ *   4. For j = 0 .. D - 1 in that order, one kcc_deploy step on the current state, exactly as
+ *      defined above: spec = shape j, replicas = shape_count[j], no node_cap, no groups (every
+ *      row is eligible; the drained ones are full), the call's policy.  shape_placed[j],
+ *      shape_nodes[j], shape_err[j] are that step's placed, nodes_used and step_err.  A shape
+ *      with a zero cpu or memory request that meets a row with free CPU or memory is a flagged
+ *      step (KCC_SPEC_DIVZERO, nothing placed), as everywhere in this library; the steps after
+ *      it run.  summary[2] = D, summary[3] = the sum of shape_placed.  Entries j >= D of all
+ *      seven shape arrays are 0.
+ *   5. D > M: summary[2] = -1, summary[3] = 0, all seven shape arrays 0, nothing placed; the
+ *      drained rows are still left full and summary[0], summary[1] still hold.
+ *
+ * n_nodes, n_ext and policy as kcc_deploy's; max_shapes outside [1, KCC_DRAIN_MAX_SHAPES],
+ * n_pods outside [0, 2^31 - 4096], a NULL required array (drain with n_nodes > 0 included):
+ * KCC_EINVAL.  n_nodes == 0: KCC_OK, summary and shape outputs 0 (pods without nodes:
+ * KCC_EINVAL).  n_pods == 0: the drained rows are left full, summary = {rows, 0, 0, 0}.
+ * The host form validates the CSR (offset 0 first, non-decreasing, n_pods last; else
+ * KCC_EINVAL), runs on the context's device 0, retains no caller pointer, writes the four state
+ * arrays back, and enqueues the D steps alone (it reads D back).  The async form takes device
+ * pointers and clamps the CSR offsets into range (a malformed CSR gives wrong numbers, never a
+ * fault); it only enqueues, never reads a device value on the host and allocates only when a
+ * size exceeds every earlier call's.  It runs max_shapes deploy steps, the ones past D being
+ * padding steps (spec (1, 1), 0 replicas) that place nothing, so the number and kind of its
+ * launches depend only on (N, P, R, policy, max_shapes) and it can be captured into one linear
+ * graph with the kcc_fit*_async call that follows: size max_shapes to the cluster, every
+ * padding step costs a deploy step's launches.  Both forms give identical outputs.  No kernel
+ * of it waits on another workgroup: it neither sets nor reads the fault words.
+ * ------------------------------------------------------------------------- */
+#define KCC_DRAIN_MAX_SHAPES 4096
+#define KCC_DRAIN_SUMMARY 4 /* drained rows, evicted pods, shapes (or -1), placed pods */
+int kcc_drain(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+              const int64_t* alloc_pods, int64_t n_ext, const int64_t* alloc_x /* [R * N] */,
+              int64_t* pod_count, uint64_t* used_cpu, int64_t* used_mem,
+              int64_t* used_x /* [R * N] */, const uint8_t* drain /* [N] */, int64_t n_pods,
+              const int64_t* node_pod_ptr /* [N + 1] */, const uint64_t* pod_cpu /* [P] */,
+              const int64_t* pod_mem /* [P] */, const int64_t* pod_x /* [R * P], nullable */,
+              const uint8_t* pod_movable /* [P], nullable */, int policy, int64_t max_shapes,
+              int64_t* summary /* [KCC_DRAIN_SUMMARY] */, uint64_t* shape_cpu, int64_t* shape_mem,
+              int64_t* shape_x /* [R * max_shapes] */, int64_t* shape_count,
+              int64_t* shape_placed, int64_t* shape_nodes,
+              int32_t* shape_err /* each [max_shapes] */);
+int kcc_drain_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                    const int64_t* d_alloc_mem, const int64_t* d_alloc_pods, int64_t n_ext,
+                    const int64_t* d_alloc_x, int64_t* d_pod_count, uint64_t* d_used_cpu,
+                    int64_t* d_used_mem, int64_t* d_used_x, const uint8_t* d_drain,
+                    int64_t n_pods, const int64_t* d_node_pod_ptr, const uint64_t* d_pod_cpu,
+                    const int64_t* d_pod_mem, const int64_t* d_pod_x,
+                    const uint8_t* d_pod_movable, int policy, int64_t max_shapes,
+                    int64_t* d_summary, uint64_t* d_shape_cpu, int64_t* d_shape_mem,
+                    int64_t* d_shape_x, int64_t* d_shape_count, int64_t* d_shape_placed,
+                    int64_t* d_shape_nodes, int32_t* d_shape_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

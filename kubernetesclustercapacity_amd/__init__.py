@@ -7,14 +7,15 @@ CapacityEngine loads libkcc.so and fails loudly if it is missing.
 """
 from ._lib import KCC_EXT_MAX  # noqa: F401  (extra resources of CapacityEngine.fit_ext)
 from ._lib import KCC_DEPLOY_PACK, KCC_DEPLOY_SPREAD  # noqa: F401  (CapacityEngine.deploy)
+from ._lib import KCC_DRAIN_MAX_SHAPES  # noqa: F401  (CapacityEngine.drain)
 from ._lib import (KCC_WHY_CAP, KCC_WHY_CPU, KCC_WHY_EXT0, KCC_WHY_MEM,  # noqa: F401
                    KCC_WHY_PODS, KCC_WHY_SLOTS)  # (CapacityEngine.fit_explain)
-from .engine import (CapacityEngine, DeployResult, ExplainResult, KccError,  # noqa: F401
-                     RequestSums, explain_groups, select_groups, verdict)
+from .engine import (CapacityEngine, DeployResult, DrainResult, ExplainResult,  # noqa: F401
+                     KccError, RequestSums, explain_groups, select_groups, verdict)
 from .shard import node_range, shard_bounds  # noqa: F401
 
-__all__ = ["CapacityEngine", "KccError", "RequestSums", "DeployResult", "ExplainResult", "verdict",
-           "select_groups", "explain_groups", "node_range",
+__all__ = ["CapacityEngine", "KccError", "RequestSums", "DeployResult", "DrainResult",
+           "ExplainResult", "verdict", "select_groups", "explain_groups", "node_range",
            "shard_bounds", "KCC_EXT_MAX", "KCC_DEPLOY_PACK", "KCC_DEPLOY_SPREAD",
-           "KCC_WHY_SLOTS", "KCC_WHY_CPU", "KCC_WHY_MEM", "KCC_WHY_EXT0", "KCC_WHY_PODS",
-           "KCC_WHY_CAP"]
+           "KCC_DRAIN_MAX_SHAPES", "KCC_WHY_SLOTS", "KCC_WHY_CPU", "KCC_WHY_MEM", "KCC_WHY_EXT0",
+           "KCC_WHY_PODS", "KCC_WHY_CAP"]

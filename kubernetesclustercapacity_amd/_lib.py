@@ -43,6 +43,9 @@ KCC_DEPLOY_SPREAD = 1
 KCC_DEPLOY_TILE = 1024
 KCC_DEPLOY_SCAN_PASS = 256
 KCC_LEVELS_MAX = 8  # include/kcc.h: priority levels of kcc_reduce_requests_levels / kcc_fit_levels
+# kcc_drain (include/kcc.h): the most distinct pod shapes a call takes, the words of its summary
+KCC_DRAIN_MAX_SHAPES = 4096
+KCC_DRAIN_SUMMARY = 4
 
 _i64, _i32, _int, _vp, _dbl = C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_double
 
@@ -126,6 +129,10 @@ SIGNATURES = {
                        + [_i64, _i64] + [_vp] * 7),
     "kcc_fit_levels_async": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 3 + [_i64]
                              + [_vp] * 3 + [_i64, _i64] + [_vp] * 8),
+    "kcc_drain": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64] + [_vp] * 5
+                  + [_int, _i64] + [_vp] * 8),
+    "kcc_drain_async": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64] + [_vp] * 5
+                        + [_int, _i64] + [_vp] * 9),
 }
 
 # per-string status of kcc_parse_* (include/kcc.h)

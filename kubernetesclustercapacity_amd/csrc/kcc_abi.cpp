@@ -132,6 +132,7 @@ struct Dev {
   DevBuf lv_tot, lv_err, lv_x;     // kcc_fit_levels: one level's cells [G S_l], spec_x by level
   DevBuf f_cap, f_present, f_flag;   // kcc::FoldWork (kcc_spread_fold)
   DevBuf dp_a, dp_tsum, dp_toff, dp_flag, dp_st, dp_bins;  // kcc::DeployWork (kcc_deploy)
+  DevBuf dr_tab, dr_plan;  // kcc::DrainWork (kcc_drain): meta / cnt / rep; the plan and its outputs
   DevBuf kb_counts, kb_tot, kb_sr, kb_sv;  // kcc::KeyedWork (bucketed keyed reduce)
   DevBuf kb_part, kb_arrive;               // one-sweep gather: part rows, arrivals (zeroed)
   DevBuf kb_esc_n, kb_esc_row, kb_esc_cpu, kb_esc_mem;
@@ -2743,6 +2744,179 @@ int kcc_fit_levels(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
       (rc = st.in(sp.spec_x, nd.R * S)) || (rc = st.in(sp.node_cap, S)) ||
       (rc = st.out(totals, cells)) || (rc = st.out(spec_err, cells)) ||
       (rc = fit_levels_dev(ctx, dv, nd, sp, n_levels, level_ptr, totals, spec_err, dv.stream)))
+    return rc;
+  return st.finish();
+}
+
+}  // extern "C"
+
+
+// ---- drain what-if: the pods of drained rows re-placed (kcc_drain.hip) --------------------
+
+namespace {
+
+struct DrainArgs {
+  kcc::FitNodes nd;  // pod_count / used_* left nullptr: the state is the four pointers below
+  int64_t* pod_count;
+  uint64_t* used_cpu;
+  int64_t* used_mem;
+  int64_t* used_x;
+  const uint8_t* drain;
+  kcc::DrainPods pods;
+  int policy;
+  int64_t max_shapes;
+  kcc::DrainOut out;
+};
+
+// Argument checks of both entry points (host or device pointers alike).
+int check_drain(kcc_ctx* ctx, const DrainArgs& a) {
+  const kcc::FitNodes& nd = a.nd;
+  const int64_t P = a.pods.P;
+  if (nd.n < 0 || P < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (a.policy != KCC_DEPLOY_PACK && a.policy != KCC_DEPLOY_SPREAD)
+    return fail(ctx, KCC_EINVAL, "policy must be KCC_DEPLOY_PACK or KCC_DEPLOY_SPREAD");
+  if (nd.R < 0 || nd.R > KCC_EXT_MAX) return fail(ctx, KCC_EINVAL, "n_ext must be in [0, KCC_EXT_MAX]");
+  if (a.max_shapes < 1 || a.max_shapes > KCC_DRAIN_MAX_SHAPES)
+    return fail(ctx, KCC_EINVAL, "max_shapes must be in [1, KCC_DRAIN_MAX_SHAPES]");
+  if (nd.n > kcc::GRP_MAX_NODES) return fail(ctx, KCC_EINVAL, "too many nodes (max 2^31 - 4096)");
+  if (P > kcc::DRAIN_MAX_PODS) return fail(ctx, KCC_EINVAL, "too many pods (max 2^31 - 4096)");
+  if (nd.n == 0 && P != 0) return fail(ctx, KCC_EINVAL, "pods without nodes");
+  const kcc::DrainOut& o = a.out;
+  if (!o.summary || !o.shape_cpu || !o.shape_mem || !o.shape_count || !o.shape_placed ||
+      !o.shape_nodes || !o.shape_err || (nd.R > 0 && !o.shape_x))
+    return fail(ctx, KCC_EINVAL, "NULL output");
+  if (nd.n > 0 && (!nd.alloc_cpu || !nd.alloc_mem || !nd.alloc_pods || !a.pod_count ||
+                   !a.used_cpu || !a.used_mem || !a.drain || !a.pods.node_pod_ptr))
+    return fail(ctx, KCC_EINVAL, "NULL node array");
+  if (nd.R > 0 && nd.n > 0 && (!nd.alloc_x || !a.used_x))
+    return fail(ctx, KCC_EINVAL, "NULL extra-resource array with n_ext > 0");
+  if (P > 0 && (!a.pods.pod_cpu || !a.pods.pod_mem)) return fail(ctx, KCC_EINVAL, "NULL pod array");
+  return KCC_OK;
+}
+
+// Device level: the checks, the degenerate case, the workspaces (they only grow) and the
+// launches on s.  host_form: D is read back after the pod pass (one synchronisation of s) and
+// the plan has D steps; else max_shapes steps, the ones behind D padding.
+int drain_dev(kcc_ctx* ctx, Dev& dv, const DrainArgs& a, hipStream_t s, bool host_form) {
+  const int rc = check_drain(ctx, a);
+  if (rc) return rc;
+  const size_t M = (size_t)a.max_shapes, R = (size_t)a.nd.R;
+  const kcc::DrainOut& o = a.out;
+  if (a.nd.n == 0) {  // no rows: nothing drained, nothing evicted
+    KCC_HIP(ctx, hipMemsetAsync(o.summary, 0, 8 * KCC_DRAIN_SUMMARY, s));
+    KCC_HIP(ctx, hipMemsetAsync(o.shape_cpu, 0, 8 * M, s));
+    KCC_HIP(ctx, hipMemsetAsync(o.shape_mem, 0, 8 * M, s));
+    if (R) KCC_HIP(ctx, hipMemsetAsync(o.shape_x, 0, 8 * R * M, s));
+    KCC_HIP(ctx, hipMemsetAsync(o.shape_count, 0, 8 * M, s));
+    KCC_HIP(ctx, hipMemsetAsync(o.shape_placed, 0, 8 * M, s));
+    KCC_HIP(ctx, hipMemsetAsync(o.shape_nodes, 0, 8 * M, s));
+    KCC_HIP(ctx, hipMemsetAsync(o.shape_err, 0, 4 * M, s));
+    return KCC_OK;
+  }
+  const size_t T = (size_t)kcc::drain_table(a.max_shapes);
+  KCC_HIP(ctx, ensure(dv.dr_tab, 8 * kcc::DRAIN_META_WORDS + 8 * T));
+  // plan_cpu, plan_mem, plan_rep, placed, nodes_used [M], plan_x [R M] (int64), step_err [M]
+  KCC_HIP(ctx, ensure(dv.dr_plan, 8 * M * (5 + R) + 4 * M));
+  kcc::DrainWork w;
+  w.meta = as<unsigned long long>(dv.dr_tab);
+  w.cnt = reinterpret_cast<uint32_t*>(w.meta + kcc::DRAIN_META_WORDS);
+  w.rep = reinterpret_cast<int32_t*>(w.cnt + T);
+  w.plan_cpu = as<uint64_t>(dv.dr_plan);
+  w.plan_mem = reinterpret_cast<int64_t*>(w.plan_cpu + M);
+  w.plan_rep = w.plan_mem + M;
+  w.placed = w.plan_rep + M;
+  w.nodes_used = w.placed + M;
+  w.plan_x = w.nodes_used + M;
+  w.step_err = reinterpret_cast<int32_t*>(w.plan_x + R * M);
+  KCC_HIP(ctx, kcc::launch_drain_scan(a.nd, a.pod_count, a.used_cpu, a.used_mem, a.used_x, a.drain,
+                                      a.pods, a.max_shapes, w, s));
+  int64_t K = a.max_shapes;
+  if (host_form) {
+    unsigned long long meta[kcc::DRAIN_META_WORDS];
+    KCC_HIP(ctx, hipMemcpyAsync(meta, w.meta, sizeof(meta), hipMemcpyDeviceToHost, s));
+    KCC_HIP(ctx, hipStreamSynchronize(s));
+    const bool over = meta[kcc::DRAIN_META_OVERFLOW] != 0 ||
+                      meta[kcc::DRAIN_META_CLAIMED] > (unsigned long long)a.max_shapes;
+    K = over ? 0 : (int64_t)meta[kcc::DRAIN_META_CLAIMED];
+  }
+  KCC_HIP(ctx, kcc::launch_drain_plan(a.nd.R, a.pods, a.max_shapes, K, w, o, s));
+  if (K > 0) {
+    const DeployArgs d{{a.nd.n, a.nd.alloc_cpu, a.nd.alloc_mem, a.nd.alloc_pods, nullptr, nullptr,
+                        nullptr, a.nd.R, a.nd.alloc_x, nullptr, nullptr, 1},
+                       a.pod_count, a.used_cpu, a.used_mem, a.used_x, nullptr,
+                       {K, w.plan_cpu, w.plan_mem, w.plan_x, w.plan_rep, nullptr, a.policy},
+                       w.placed, w.nodes_used, w.step_err, nullptr};
+    const int drc = deploy_dev(ctx, dv, d, s);
+    if (drc) return drc;
+  }
+  KCC_HIP(ctx, kcc::launch_drain_finish(a.max_shapes, w, o, s));
+  return KCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kcc_drain_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                    const int64_t* d_alloc_mem, const int64_t* d_alloc_pods, int64_t n_ext,
+                    const int64_t* d_alloc_x, int64_t* d_pod_count, uint64_t* d_used_cpu,
+                    int64_t* d_used_mem, int64_t* d_used_x, const uint8_t* d_drain,
+                    int64_t n_pods, const int64_t* d_node_pod_ptr, const uint64_t* d_pod_cpu,
+                    const int64_t* d_pod_mem, const int64_t* d_pod_x,
+                    const uint8_t* d_pod_movable, int policy, int64_t max_shapes,
+                    int64_t* d_summary, uint64_t* d_shape_cpu, int64_t* d_shape_mem,
+                    int64_t* d_shape_x, int64_t* d_shape_count, int64_t* d_shape_placed,
+                    int64_t* d_shape_nodes, int32_t* d_shape_err, void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  const DrainArgs a{{n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, nullptr, nullptr, nullptr,
+                     n_ext, d_alloc_x, nullptr, nullptr, 1},
+                    d_pod_count, d_used_cpu, d_used_mem, d_used_x, d_drain,
+                    {n_pods, d_node_pod_ptr, d_pod_cpu, d_pod_mem, d_pod_x, d_pod_movable},
+                    policy, max_shapes,
+                    {d_summary, d_shape_cpu, d_shape_mem, d_shape_x, d_shape_count, d_shape_placed,
+                     d_shape_nodes, d_shape_err}};
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  return drain_dev(ctx, dv, a, static_cast<hipStream_t>(stream), false);
+}
+
+int kcc_drain(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const int64_t* alloc_mem,
+              const int64_t* alloc_pods, int64_t n_ext, const int64_t* alloc_x,
+              int64_t* pod_count, uint64_t* used_cpu, int64_t* used_mem, int64_t* used_x,
+              const uint8_t* drain, int64_t n_pods, const int64_t* node_pod_ptr,
+              const uint64_t* pod_cpu, const int64_t* pod_mem, const int64_t* pod_x,
+              const uint8_t* pod_movable, int policy, int64_t max_shapes, int64_t* summary,
+              uint64_t* shape_cpu, int64_t* shape_mem, int64_t* shape_x, int64_t* shape_count,
+              int64_t* shape_placed, int64_t* shape_nodes, int32_t* shape_err) {
+  if (!ctx) return KCC_EINVAL;
+  DrainArgs a{{n_nodes, alloc_cpu, alloc_mem, alloc_pods, nullptr, nullptr, nullptr, n_ext,
+               alloc_x, nullptr, nullptr, 1},
+              pod_count, used_cpu, used_mem, used_x, drain,
+              {n_pods, node_pod_ptr, pod_cpu, pod_mem, pod_x, pod_movable},
+              policy, max_shapes,
+              {summary, shape_cpu, shape_mem, shape_x, shape_count, shape_placed, shape_nodes,
+               shape_err}};
+  int rc = check_drain(ctx, a);
+  if (rc) return rc;
+  // the host form reads the offsets: the CSR is well formed
+  if ((rc = check_csr(ctx, n_nodes, n_pods, node_pod_ptr))) return rc;
+  const int64_t n = n_nodes, P = n_pods, R = n_ext, M = max_shapes;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  Stage st(ctx, dv);
+  kcc::DrainOut& o = a.out;
+  if ((rc = st.in(a.nd.alloc_cpu, n)) || (rc = st.in(a.nd.alloc_mem, n)) ||
+      (rc = st.in(a.nd.alloc_pods, n)) || (rc = st.in(a.nd.alloc_x, R * n)) ||
+      (rc = st.in(a.drain, n)) || (rc = st.in(a.pods.node_pod_ptr, csr_len(n))) ||
+      (rc = st.in(a.pods.pod_cpu, P)) || (rc = st.in(a.pods.pod_mem, P)) ||
+      (rc = st.in(a.pods.pod_x, R * P)) || (rc = st.in(a.pods.movable, P)) ||
+      (rc = st.inout(a.pod_count, n)) || (rc = st.inout(a.used_cpu, n)) ||
+      (rc = st.inout(a.used_mem, n)) || (rc = st.inout(a.used_x, R * n)) ||
+      (rc = st.out(o.summary, KCC_DRAIN_SUMMARY)) || (rc = st.out(o.shape_cpu, M)) ||
+      (rc = st.out(o.shape_mem, M)) || (rc = st.out(o.shape_x, R * M)) ||
+      (rc = st.out(o.shape_count, M)) || (rc = st.out(o.shape_placed, M)) ||
+      (rc = st.out(o.shape_nodes, M)) || (rc = st.out(o.shape_err, M)) ||
+      (rc = drain_dev(ctx, dv, a, dv.stream, true)))
     return rc;
   return st.finish();
 }

@@ -990,6 +990,65 @@ hipError_t launch_deploy(const FitNodes& nd, int64_t* pod_count, uint64_t* used_
                          const DeployWork& w, int64_t* placed, int64_t* nodes_used,
                          int32_t* step_err, int64_t* placed_rows, hipStream_t s);
 
+// ---- drain what-if: the pods of drained rows as a deploy plan (kcc_drain.hip)
+constexpr int64_t DRAIN_MAX_SHAPES = 4096;                     // include/kcc.h KCC_DRAIN_MAX_SHAPES
+constexpr int64_t DRAIN_MAX_PODS = ((int64_t)1 << 31) - 4096;  // a slot holds a pod index (int32)
+// the call's counters, zeroed by launch_drain_scan: drained rows, evicted pods, claimed
+// slots, and the overflow word (more than max_shapes shapes, or a probe that found no slot)
+enum { DRAIN_META_ROWS = 0, DRAIN_META_EVICTED = 1, DRAIN_META_CLAIMED = 2, DRAIN_META_OVERFLOW = 3,
+       DRAIN_META_WORDS = 8 };
+// slots of the shape table: a power of two, at least twice max_shapes and one workgroup's 256
+inline int64_t drain_table(int64_t max_shapes) {
+  int64_t T = 256;
+  while (T < 2 * max_shapes) T <<= 1;
+  return T;
+}
+struct DrainPods {
+  int64_t P;
+  const int64_t* node_pod_ptr;  // [n + 1], clamped into [0, P] where read
+  const uint64_t* pod_cpu;      // [P]
+  const int64_t* pod_mem;       // [P]
+  const int64_t* pod_x;         // [R, P], nullable: zeros
+  const uint8_t* movable;       // [P], nullable: every pod movable
+};
+struct DrainWork {
+  int32_t* rep;               // [drain_table(M)] a slot's representative pod (-1: empty)
+  uint32_t* cnt;              // [drain_table(M)] the slot's pods
+  unsigned long long* meta;   // [DRAIN_META_WORDS]
+  // the plan kcc::launch_deploy reads (M = max_shapes entries each, plan_x [R, K]) and the
+  // steps' outputs
+  uint64_t* plan_cpu;
+  int64_t* plan_mem;
+  int64_t* plan_x;
+  int64_t* plan_rep;
+  int64_t* placed;
+  int64_t* nodes_used;
+  int32_t* step_err;
+};
+struct DrainOut {
+  int64_t* summary;  // [4]
+  uint64_t* shape_cpu;
+  int64_t* shape_mem;
+  int64_t* shape_x;  // [R, M]
+  int64_t* shape_count;
+  int64_t* shape_placed;
+  int64_t* shape_nodes;
+  int32_t* shape_err;
+};
+// The table and counters reset, dr_rows (the drained rows of the four state arrays left full)
+// and dr_pods.  nd.n >= 1; nd's pod_count / used_* are not read.
+hipError_t launch_drain_scan(const FitNodes& nd, int64_t* pod_count, uint64_t* used_cpu,
+                             int64_t* used_mem, int64_t* used_x, const uint8_t* drain,
+                             const DrainPods& pods, int64_t max_shapes, const DrainWork& w,
+                             hipStream_t s);
+// dr_plan: the shape key outputs [max_shapes] and a plan of K <= max_shapes steps (K >= D; the
+// steps behind D are padding steps).  On overflow every step is a padding step.
+hipError_t launch_drain_plan(int64_t R, const DrainPods& pods, int64_t max_shapes, int64_t K,
+                             const DrainWork& w, const DrainOut& out, hipStream_t s);
+// dr_finish: the steps' outputs masked to j < D, and the summary.
+hipError_t launch_drain_finish(int64_t max_shapes, const DrainWork& w, const DrainOut& out,
+                               hipStream_t s);
+
 // ---- opt-in scheduler request model (kcc_pods.hip) ---------------
 hipError_t launch_pod_requests(int64_t n_pods, int64_t n_cont, int64_t n_init,
                                const int64_t* pod_ptr, const uint64_t* cpu_req,

@@ -74,6 +74,29 @@ class DeployResult:
 
 
 @dataclass
+class DrainResult:
+    """What CapacityEngine.drain returns: the summary (drained rows, evicted pods, distinct
+    shapes — -1 when they exceed max_shapes and nothing was placed — and placed pods), the
+    shape arrays trimmed to the shapes found (descending; shape_x is [R, D]) and the node state
+    after the drain."""
+    drained_rows: int
+    evicted: int
+    shapes: int
+    placed: int
+    shape_cpu: np.ndarray
+    shape_mem: np.ndarray
+    shape_x: np.ndarray
+    shape_count: np.ndarray
+    shape_placed: np.ndarray
+    shape_nodes: np.ndarray
+    shape_err: np.ndarray
+    pod_count: np.ndarray
+    used_cpu: np.ndarray
+    used_mem: np.ndarray
+    used_x: np.ndarray
+
+
+@dataclass
 class ExplainResult:
     """What CapacityEngine.fit_explain returns: fit_capped's totals / err, the rows and the
     replicas of each cell by reason ([KCC_WHY_SLOTS, G, S]) and what stays free ([2 + R, G, S]);
@@ -525,6 +548,82 @@ class CapacityEngine:
             _dp(eligible), k, _dp(spec_cpu), _dp(spec_mem), _dp(spec_x), _dp(replicas),
             _dp(node_cap), int(policy), _dp(placed), _dp(nodes_used), _dp(step_err),
             _dp(placed_rows), _stream(stream)))
+
+    # -- drain what-if: the pods of drained rows re-placed (opt-in) -------
+    def drain(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem, drain,
+              node_pod_ptr, pod_cpu, pod_mem, policy=_lib.KCC_DEPLOY_SPREAD, alloc_x=None,
+              used_x=None, pod_x=None, pod_movable=None,
+              max_shapes=_lib.KCC_DRAIN_MAX_SHAPES) -> "DrainResult":
+        """Rows with drain[i] != 0 go away: their state is left full (used = allocatable, so
+        every fit gives them 0), and the movable pods that ran on them (pods grouped by node,
+        node_pod_ptr [N + 1]; pod_movable None: all) are bucketed by request shape (pod_cpu,
+        pod_mem, pod_x[:, p]) and placed on the other rows, one deploy step per shape, biggest
+        shape first, under `policy`.  More than max_shapes distinct shapes: shapes = -1, nothing
+        placed.  The inputs are not modified: the result carries the updated state."""
+        a = [_arr(x, t) for x, t in zip((alloc_cpu, alloc_mem, alloc_pods),
+                                        (np.uint64, np.int64, np.int64))]
+        st = [np.array(x, dtype=t, order="C", copy=True)
+              for x, t in zip((pod_count, used_cpu, used_mem), (np.int64, np.uint64, np.int64))]
+        n = a[0].size
+        dr = _arr(np.asarray(drain) != 0, np.uint8)
+        if any(x.shape != (n,) for x in a + st + [dr]):
+            raise ValueError("node arrays differ in length")
+        pc, pm = _arr(pod_cpu, np.uint64), _arr(pod_mem, np.int64)
+        P = pc.size
+        if pc.shape != (P,) or pm.shape != (P,):
+            raise ValueError("pod arrays differ in length")
+        ptr = _arr(node_pod_ptr, np.int64)
+        if n > 0 and ptr.shape != (n + 1,):
+            raise ValueError("node_pod_ptr must be [N + 1]")
+        ax = _arr(np.zeros((0, n)) if alloc_x is None else alloc_x, np.int64)
+        ux = np.array(np.zeros((0, n)) if used_x is None else used_x, dtype=np.int64, order="C",
+                      copy=True)
+        if ax.ndim != 2 or ux.shape != ax.shape or ax.shape[1] != n:
+            raise ValueError("alloc_x and used_x must both be [R, N]")
+        R = ax.shape[0]
+        px = None if pod_x is None else _arr(pod_x, np.int64)
+        if px is not None and px.shape != (R, P):
+            raise ValueError("pod_x must be [R, P]")
+        mv = None if pod_movable is None else _arr(np.asarray(pod_movable) != 0, np.uint8)
+        if mv is not None and mv.shape != (P,):
+            raise ValueError("pod_movable must be [P]")
+        M = int(max_shapes)
+        m = max(M, 0)
+        summary = np.zeros(_lib.KCC_DRAIN_SUMMARY, np.int64)
+        s_cpu = np.zeros(m, np.uint64)
+        s_mem, s_cnt, s_pl, s_nd = (np.zeros(m, np.int64) for _ in range(4))
+        s_x = np.zeros((R, m), np.int64)
+        s_err = np.zeros(m, np.int32)
+        self._check(self._lib.kcc_drain(
+            self._h, n, *[_p(x) for x in a], R, _p(ax), _p(st[0]), _p(st[1]), _p(st[2]), _p(ux),
+            _p(dr), P, _p(ptr), _p(pc), _p(pm), _p(px), _p(mv), int(policy), M, _p(summary),
+            _p(s_cpu), _p(s_mem), _p(s_x), _p(s_cnt), _p(s_pl), _p(s_nd), _p(s_err)))
+        D = max(int(summary[2]), 0)
+        return DrainResult(int(summary[0]), int(summary[1]), int(summary[2]), int(summary[3]),
+                           s_cpu[:D].copy(), s_mem[:D].copy(), s_x[:, :D].copy(), s_cnt[:D].copy(),
+                           s_pl[:D].copy(), s_nd[:D].copy(), s_err[:D].copy(), st[0], st[1], st[2],
+                           ux)
+
+    def drain_async(self, alloc_cpu, alloc_mem, alloc_pods, n_ext, alloc_x, pod_count, used_cpu,
+                    used_mem, used_x, drain, node_pod_ptr, pod_cpu, pod_mem, pod_x, pod_movable,
+                    policy, max_shapes, summary, shape_cpu, shape_mem, shape_x, shape_count,
+                    shape_placed, shape_nodes, shape_err, stream=None):
+        """Device form of drain (torch tensors on the engine's device): pod_count, used_cpu,
+        used_mem and used_x (n_ext * N, resource-major) are updated in place; drain and
+        pod_movable uint8; summary int64 [4]; the shape arrays int64 [max_shapes] (shape_x
+        n_ext * max_shapes, shape_err int32), untrimmed: entries behind summary[2] are 0.  Only
+        enqueues on `stream`, max_shapes deploy steps whatever the pods hold: it can be captured
+        into one graph with the fit_*_async call that follows it.  The arguments go to the
+        C-ABI as they are (None: NULL), which validates them."""
+        n = 0 if alloc_cpu is None else alloc_cpu.numel()
+        p = 0 if pod_cpu is None else pod_cpu.numel()
+        self._check(self._lib.kcc_drain_async(
+            self._h, n, _dp(alloc_cpu), _dp(alloc_mem), _dp(alloc_pods), int(n_ext), _dp(alloc_x),
+            _dp(pod_count), _dp(used_cpu), _dp(used_mem), _dp(used_x), _dp(drain), p,
+            _dp(node_pod_ptr), _dp(pod_cpu), _dp(pod_mem), _dp(pod_x), _dp(pod_movable),
+            int(policy), int(max_shapes), _dp(summary), _dp(shape_cpu), _dp(shape_mem),
+            _dp(shape_x), _dp(shape_count), _dp(shape_placed), _dp(shape_nodes), _dp(shape_err),
+            _stream(stream)))
 
     def capacity(self, node_ptr, cpu_req, mem_req, alloc_cpu, alloc_mem, alloc_pods, pod_count,
                  spec_cpu, spec_mem):
