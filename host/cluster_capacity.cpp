@@ -55,6 +55,21 @@
 // with -deploy, -priority, -schedulerRequests and -v it is refused.  A name no node carries is
 // an error (exit status 1).  An unhealthy node among the named ones is not drained and not
 // counted: its row is a zero row already (CC:221-226) and the reference lists no pods for it.
+// -consolidate all | below=<pct> | node=<a,b,...> (opt-in): the removal what-if.  For each
+// candidate node ON ITS OWN, its pods (requests and `daemon` pods as -drain's) are placed on the
+// other nodes as they stand by kcc_consolidate, first fit in node order.  below=<pct>: the healthy
+// nodes whose cpu AND memory request utilisation are both below pct per cent (used * 100 < pct *
+// alloc, in integers: an autoscaler's scale-down threshold); an unhealthy node is never a
+// candidate.  After the echo line (CC:85), one line per candidate in node order, "Node <name> :
+// <e> pods evicted, <p> placed, <u> not placed, <z> without requests", then "Removable one at a
+// time : <k> of <C> nodes (<k2> counting pods without requests as placed)".  A candidate with
+// more than KCC_CONS_MAX_PODS evicted pods is not evaluated: its line is "Node <name> : <e> pods
+// evicted, more than 1024: not evaluated", and it counts in <C> but never as removable.  The state is only
+// read: every later number is what it is without the flag.  Nodes removable one at a time need
+// not be removable together: -drain node=<those> is the joint check.  It composes with -specs,
+// -byPool, -extRequests, -maxPerNode, -explain and -spreadBy zone; with -drain, -deploy,
+// -priority, -schedulerRequests and -v it is refused.  A name no node carries is an error (exit
+// status 1).
 #include <array>
 #include <cctype>
 #include <cerrno>
@@ -91,7 +106,7 @@ struct Flags {
       {"byPool", "false"},        {"extRequests", ""},      {"maxPerNode", "0"},
       {"spreadBy", ""},           {"maxSkew", "1"},         {"deploy", ""},
       {"explain", "false"},       {"priority", ""},         {"drain", ""},
-      {"drainPolicy", "spread"}};
+      {"drainPolicy", "spread"}, {"consolidate", ""}};
 };
 
 // Go flag package syntax: -name=value, -name value, --name=value; bool -v.
@@ -466,6 +481,40 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  // opt-in removal what-if (NOT the reference's arithmetic): the candidate nodes
+  const bool consOn = !f.v["consolidate"].empty();
+  std::string consKind;  // all, below or node
+  std::vector<std::string> consNames;
+  int64_t consPct = 0;
+  if (consOn) {
+    const std::string& d = f.v["consolidate"];
+    const size_t eq = d.find('=');
+    consKind = eq == std::string::npos ? d : d.substr(0, eq);
+    bool ok = (consKind == "all" && eq == std::string::npos) ||
+              ((consKind == "below" || consKind == "node") && eq != std::string::npos && eq + 1 < d.size());
+    if (ok && consKind == "below") {
+      const std::string v = d.substr(eq + 1);
+      ok = v.size() <= 9 && v.find_first_not_of("0123456789") == std::string::npos;
+      if (ok) consPct = std::atoll(v.c_str());
+    }
+    if (ok && consKind == "node") {
+      std::istringstream is(d.substr(eq + 1));
+      std::string item;
+      while (std::getline(is, item, ','))
+        if (!item.empty()) consNames.push_back(item);
+      ok = !consNames.empty();
+    }
+    if (!ok) {
+      std::fprintf(stderr, "invalid value \"%s\" for flag -consolidate: want all, below=<pct> or node=<a,b,...>\n",
+                   d.c_str());
+      return 2;
+    }
+    const char* with = drainOn ? "-drain" : deployOn ? "-deploy" : prioOn ? "-priority" : schedReq ? "-schedulerRequests" : verbose ? "-v" : nullptr;
+    if (with) {
+      std::fprintf(stderr, "-consolidate cannot be combined with %s: each candidate's pods are placed on the per-node app-container sums as they stand, and the state is left alone\n", with);
+      return 2;
+    }
+  }
   std::vector<Step> plan;
   if (deployOn) {
     if (verbose) {
@@ -670,6 +719,29 @@ int main(int argc, char** argv) {
     sum_ = eum;
   }
 
+  // -drain and -consolidate: every counted pod's request (the sum of its app containers,
+  // CC:276-294; px [R * P] from the -extRequests columns) and whether it can move (no `daemon`
+  // line)
+  const auto podRequests = [&](std::vector<uint64_t>& pcpu, std::vector<int64_t>& pmem,
+                               std::vector<int64_t>& px, std::vector<uint8_t>& movable) {
+    const size_t P = in.pod_daemon.size(), R = (size_t)ext.R();
+    pcpu.assign(P, 0);
+    pmem.assign(P, 0);
+    px.assign(R * P, 0);
+    movable.resize(P);
+    for (size_t p = 0; p < P; ++p) {
+      movable[p] = in.pod_daemon[p] ? 0 : 1;
+      for (int64_t k = in.lv_pod_ptr[p]; k < in.lv_pod_ptr[p + 1]; ++k) {
+        pcpu[p] += in.cpu_req[(size_t)k];
+        pmem[p] = (int64_t)((uint64_t)pmem[p] + (uint64_t)in.mem_req[(size_t)k]);
+        const auto it = ext.creq.find(in.app[(size_t)k]);
+        if (it == ext.creq.end()) continue;
+        for (size_t r = 0; r < R; ++r)
+          px[r * P + p] = (int64_t)((uint64_t)px[r * P + p] + (uint64_t)it->second[r]);
+      }
+    }
+  };
+
   // -drain: the rows of the named pool, zone or nodes go away.  Row i is node i's; a pod's
   // request is the sum of its app containers (CC:276-294), a `daemon` pod goes away with its
   // node.  kcc_drain leaves the drained rows full and places the evicted pods on the rest;
@@ -703,20 +775,10 @@ int main(int argc, char** argv) {
       if (rc) return fail(ctx, rc);
     }
     const size_t P = in.pod_daemon.size(), R = (size_t)ext.R();
-    std::vector<uint64_t> pcpu(P, 0);
-    std::vector<int64_t> pmem(P, 0), px(R * P, 0);
-    std::vector<uint8_t> movable(P);
-    for (size_t p = 0; p < P; ++p) {
-      movable[p] = in.pod_daemon[p] ? 0 : 1;
-      for (int64_t k = in.lv_pod_ptr[p]; k < in.lv_pod_ptr[p + 1]; ++k) {
-        pcpu[p] += in.cpu_req[(size_t)k];
-        pmem[p] = (int64_t)((uint64_t)pmem[p] + (uint64_t)in.mem_req[(size_t)k]);
-        const auto it = ext.creq.find(in.app[(size_t)k]);
-        if (it == ext.creq.end()) continue;
-        for (size_t r = 0; r < R; ++r)
-          px[r * P + p] = (int64_t)((uint64_t)px[r * P + p] + (uint64_t)it->second[r]);
-      }
-    }
+    std::vector<uint64_t> pcpu;
+    std::vector<int64_t> pmem, px;
+    std::vector<uint8_t> movable;
+    podRequests(pcpu, pmem, px, movable);
     const int64_t M = KCC_DRAIN_MAX_SHAPES;
     int64_t summary[KCC_DRAIN_SUMMARY] = {0, 0, 0, 0};
     std::vector<uint64_t> shc((size_t)M);
@@ -743,6 +805,77 @@ int main(int argc, char** argv) {
     }
     suc = euc;
     sum_ = eum;
+  }
+
+  // -consolidate: for each candidate node on its own, its pods (requests and `daemon` pods as
+  // -drain's) placed on the other nodes as they stand, by kcc_consolidate.  The state is only
+  // read: the fits below are what they are without the flag.
+  if (consOn) {
+    std::vector<uint64_t> cuc(euc);
+    std::vector<int64_t> cum(eum);
+    if (!useExt) {  // the per-node request sums (CC:290-293)
+      cuc.assign((size_t)n, 0);
+      cum.assign((size_t)n, 0);
+      rc = kcc_reduce_requests(ctx, n, nc, in.node_ptr.data(), in.cpu_req.data(), in.mem_req.data(),
+                               nullptr, nullptr, cuc.data(), cum.data(), nullptr, nullptr);
+      if (rc) return fail(ctx, rc);
+    }
+    // an unhealthy node is never a candidate: its row is a zero row and lists no pods
+    std::vector<uint8_t> pick((size_t)n, 0);
+    for (int64_t i = 0; i < n; ++i) {
+      if (rows[(size_t)i].name.empty()) continue;
+      if (consKind == "all") {
+        pick[(size_t)i] = 1;
+      } else if (consKind == "below") {  // the scale-down threshold: used * 100 < pct * alloc, both
+        const unsigned __int128 uc = cuc[(size_t)i], ac = in.alloc_cpu[(size_t)i];
+        const __int128 um = cum[(size_t)i], am = in.alloc_mem[(size_t)i];
+        pick[(size_t)i] = uc * 100 < ac * (unsigned __int128)consPct && um * 100 < am * (__int128)consPct;
+      }
+    }
+    for (const std::string& want : consNames) {
+      bool found = false;
+      for (int64_t i = 0; i < n; ++i) {
+        if (cl.nodes[(size_t)i].name != want) continue;
+        if (!rows[(size_t)i].name.empty()) pick[(size_t)i] = 1;
+        found = true;
+      }
+      if (!found) {
+        std::fprintf(stderr, "-consolidate: no node with name %s in %s\n", want.c_str(), path.c_str());
+        kcc_destroy(ctx);
+        return 1;
+      }
+    }
+    std::vector<int64_t> cand;
+    for (int64_t i = 0; i < n; ++i)
+      if (pick[(size_t)i]) cand.push_back(i);
+    const size_t P = in.pod_daemon.size(), Cn = cand.size();
+    std::vector<uint64_t> pcpu;
+    std::vector<int64_t> pmem, px;
+    std::vector<uint8_t> movable;
+    podRequests(pcpu, pmem, px, movable);
+    std::vector<int64_t> cev(Cn), cpl(Cn), cze(Cn);
+    std::vector<int32_t> cer(Cn);
+    rc = kcc_consolidate(ctx, n, in.alloc_cpu.data(), in.alloc_mem.data(), in.alloc_pods.data(),
+                         ext.R(), ext.alloc_x.data(), in.pod_count.data(), cuc.data(), cum.data(),
+                         ext.used_x.data(), nullptr, (int64_t)P, in.lv_node_pod_ptr.data(),
+                         pcpu.data(), pmem.data(), px.data(), movable.data(), (int64_t)Cn,
+                         cand.data(), cev.data(), cpl.data(), cze.data(), cer.data(), nullptr);
+    if (rc) return fail(ctx, rc);
+    int64_t strict = 0, lenient = 0;
+    for (size_t j = 0; j < Cn; ++j) {
+      const char* name = cl.nodes[(size_t)cand[j]].name.c_str();
+      if (cer[j] == KCC_CAND_TOOMANY) {
+        std::printf("Node %s : %" PRId64 " pods evicted, more than %d: not evaluated\n", name, cev[j],
+                    KCC_CONS_MAX_PODS);
+        continue;
+      }
+      std::printf("Node %s : %" PRId64 " pods evicted, %" PRId64 " placed, %" PRId64 " not placed, %" PRId64
+                  " without requests\n", name, cev[j], cpl[j], cev[j] - cpl[j] - cze[j], cze[j]);
+      strict += cer[j] == KCC_CAND_OK && cpl[j] == cev[j];
+      lenient += cer[j] == KCC_CAND_OK && cpl[j] + cze[j] == cev[j];
+    }
+    std::printf("Removable one at a time : %" PRId64 " of %zu nodes (%" PRId64
+                " counting pods without requests as placed)\n", strict, Cn, lenient);
   }
 
   if (verbose) {  // CC:107-117, 137 — per-node sums and fit, one row at a time

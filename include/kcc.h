@@ -955,6 +955,101 @@ int kcc_drain_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
                     int64_t* d_shape_x, int64_t* d_shape_count, int64_t* d_shape_placed,
                     int64_t* d_shape_nodes, int32_t* d_shape_err, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Removal what-if: each candidate node's pods re-placed on the rest.  "Which of these nodes
+ * could I remove?" — the question of a cluster autoscaler's scale-down and of every cost
+ * review — asks, for each candidate node ON ITS OWN, whether the pods that run there fit on
+ * the rest of the cluster as it stands.  With every node as a candidate the same call answers
+ * "does the cluster survive the loss of any single node?".  kcc_drain answers it for one set of
+ * rows per call and rewrites the state; kcc_consolidate evaluates C candidates independently
+ * in one launch and leaves the state alone.  OPT-IN, not the reference's arithmetic; no other
+ * entry point changes.
+ * It is A placement the scheduler could make, not THE one it will make.
+ *
+ *   Node arrays as kcc_deploy's: alloc_cpu, alloc_mem, alloc_pods, n_ext = R, alloc_x [R * N].
+ *   The state, READ ONLY here: pod_count [N], used_cpu [N], used_mem [N], used_x [R * N].
+ *   target [N] (uint8, nullable): row i may receive pods iff target[i] != 0 (NULL: every row).
+ *   The pods, grouped by node, as kcc_drain's: node_pod_ptr [N + 1], pod_cpu [P], pod_mem [P],
+ *     pod_x [R * P] (nullable: zeros), pod_movable [P] (uint8, nullable: every pod movable).
+ *   cand [C]: the candidates' row indices.
+ *   Outputs: cand_evicted, cand_placed, cand_zero (int64) and cand_err (int32), each [C];
+ *     pod_target [P] (int64, nullable).
+ *
+ * Candidates are evaluated INDEPENDENTLY: each sees the state as passed in, none sees another's
+ * placements, and the other candidates are ordinary target rows.  For candidate j with row
+ * c = cand[j]:
+ *   1. c outside [0, N): cand_err[j] = KCC_CAND_BADROW, the three counts are 0 and pod_target
+ *      is not touched.
+ *   2. The evicted pods are the pods p in [node_pod_ptr[c], node_pod_ptr[c+1]), in that order,
+ *      with pod_movable == NULL or pod_movable[p] != 0.  An unmovable pod (DaemonSet, static
+ *      pod) goes away with its node.  cand_evicted[j] = their number.  Above KCC_CONS_MAX_PODS:
+ *      cand_err[j] = KCC_CAND_TOOMANY, cand_placed[j] = cand_zero[j] = 0 and the candidate's
+ *      pods keep -2 in pod_target.
+ *   3. An evicted pod with pod_cpu[p] == 0 or pod_mem[p] == 0 is counted in cand_zero[j] and
+ *      not tried (as a kcc_deploy step it is either flagged or places nothing; here it is
+ *      skipped without a row pass and the state is untouched either way).  pod_target[p] = -3.
+ *   4. The remaining evicted pods, in order, are placed exactly as kcc_deploy would place a
+ *      plan of one step per pod — spec = the pod's (cpu, mem, x[0..R)), replicas = 1, no
+ *      node_cap, KCC_DEPLOY_PACK — on a PRIVATE copy of the state.  Row i is eligible iff
+ *      i != c and (target == NULL or target[i] != 0).  A pod goes to the first eligible row in
+ *      row order whose a_i >= 1, a_i being kcc_deploy's: kcc_fit_ext's q on the current private
+ *      state, through the pod-slot clamp quirk of CC:134-136 (after all the mins; a row whose
+ *      q reaches alloc_pods takes alloc_pods - pod_count instead), negatives counted as 0.  Its
+ *      commit is kcc_deploy's with p_i = 1: used_cpu += cpu (uint64 wrap), used_mem += mem,
+ *      used_x[r] += x_r for each requested resource, pod_count += 1.  A pod with no such row is
+ *      not placed, and the pods after it are still tried.  cand_placed[j] = the placed pods;
+ *      pod_target[p] = the row, or -1.  cand_err[j] = KCC_CAND_OK.
+ *   5. pod_target, when given, is filled with -2 first: -2 marks a pod of a row that is no
+ *      candidate, an unmovable pod, or a pod of a KCC_CAND_TOOMANY candidate.
+ *   6. Duplicate entries of cand are allowed: each has its own output slot, and they write
+ *      identical pod_target values.
+ * Reading the result.  Strict: the node is removable iff cand_err == KCC_CAND_OK and
+ * cand_placed == cand_evicted.  Lenient: cand_placed + cand_zero == cand_evicted (best-effort
+ * pods, which request nothing, fit anywhere).  Nodes that are removable ONE AT A TIME need not
+ * be removable TOGETHER: two candidates may both count on the same free room.  kcc_drain with
+ * the chosen rows as its mask is the joint check.
+ * Out of scope: the pods' selectors, affinities, PodDisruptionBudgets and priorities are not
+ * read, as in kcc_drain.  There is no spread policy: an emptiest-row choice needs a full pass
+ * over the rows per pod, where first fit stops at the first row that holds the pod.
+ *
+ * KCC_EINVAL: n_ext outside [0, KCC_EXT_MAX]; n_nodes > 2^31 - 4096; n_pods outside
+ * [0, 2^31 - 4096]; n_cand negative or above 2^31 - 4096; a NULL required array (target, pod_x,
+ * pod_movable and pod_target may be NULL); pods without nodes.  n_cand == 0 or n_nodes == 0:
+ * KCC_OK, the per-candidate outputs 0 (err KCC_CAND_OK), pod_target still filled with -2.
+ * The host form validates the CSR (offset 0 first, non-decreasing, n_pods last; else
+ * KCC_EINVAL), runs on the context's device 0 and retains no caller pointer.  The async form
+ * takes device pointers and clamps the CSR offsets into range (a malformed CSR gives wrong
+ * numbers, never a fault); it only enqueues, never reads a device value on the host and
+ * allocates nothing; its launches — the fill of pod_target and one workgroup per candidate —
+ * depend only on (N, P, C, R), so it can be captured into one graph.  Both forms give
+ * identical outputs.  No kernel of it waits on another workgroup: it neither sets nor reads
+ * the fault words.
+ * ------------------------------------------------------------------------- */
+#define KCC_CONS_MAX_PODS 1024 /* evicted pods one candidate may have */
+enum { KCC_CAND_OK = 0, KCC_CAND_BADROW = 1, KCC_CAND_TOOMANY = 2 };
+int kcc_consolidate(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                    const int64_t* alloc_mem, const int64_t* alloc_pods, int64_t n_ext,
+                    const int64_t* alloc_x /* [R * N] */, const int64_t* pod_count,
+                    const uint64_t* used_cpu, const int64_t* used_mem,
+                    const int64_t* used_x /* [R * N] */, const uint8_t* target /* [N]; nullable */,
+                    int64_t n_pods, const int64_t* node_pod_ptr /* [N + 1] */,
+                    const uint64_t* pod_cpu /* [P] */, const int64_t* pod_mem /* [P] */,
+                    const int64_t* pod_x /* [R * P]; nullable */,
+                    const uint8_t* pod_movable /* [P]; nullable */, int64_t n_cand,
+                    const int64_t* cand /* [C] */, int64_t* cand_evicted, int64_t* cand_placed,
+                    int64_t* cand_zero, int32_t* cand_err /* each [C] */,
+                    int64_t* pod_target /* [P]; nullable */);
+int kcc_consolidate_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                          const int64_t* d_alloc_mem, const int64_t* d_alloc_pods, int64_t n_ext,
+                          const int64_t* d_alloc_x, const int64_t* d_pod_count,
+                          const uint64_t* d_used_cpu, const int64_t* d_used_mem,
+                          const int64_t* d_used_x, const uint8_t* d_target, int64_t n_pods,
+                          const int64_t* d_node_pod_ptr, const uint64_t* d_pod_cpu,
+                          const int64_t* d_pod_mem, const int64_t* d_pod_x,
+                          const uint8_t* d_pod_movable, int64_t n_cand, const int64_t* d_cand,
+                          int64_t* d_cand_evicted, int64_t* d_cand_placed, int64_t* d_cand_zero,
+                          int32_t* d_cand_err, int64_t* d_pod_target, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,13 @@ KCC_LEVELS_MAX = 8  # include/kcc.h: priority levels of kcc_reduce_requests_leve
 # kcc_drain (include/kcc.h): the most distinct pod shapes a call takes, the words of its summary
 KCC_DRAIN_MAX_SHAPES = 4096
 KCC_DRAIN_SUMMARY = 4
+# kcc_consolidate (include/kcc.h): the evicted pods one candidate may have, cand_err's values;
+# csrc/kcc_internal.h: the rows of one chunk of its walk (CONS_CHUNK)
+KCC_CONS_MAX_PODS = 1024
+KCC_CAND_OK = 0
+KCC_CAND_BADROW = 1
+KCC_CAND_TOOMANY = 2
+KCC_CONS_CHUNK = 1024
 
 _i64, _i32, _int, _vp, _dbl = C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_double
 
@@ -133,6 +140,10 @@ SIGNATURES = {
                   + [_int, _i64] + [_vp] * 8),
     "kcc_drain_async": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64] + [_vp] * 5
                         + [_int, _i64] + [_vp] * 9),
+    "kcc_consolidate": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64] + [_vp] * 5
+                        + [_i64] + [_vp] * 6),
+    "kcc_consolidate_async": (_int, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_i64]
+                              + [_vp] * 5 + [_i64] + [_vp] * 7),
 }
 
 # per-string status of kcc_parse_* (include/kcc.h)

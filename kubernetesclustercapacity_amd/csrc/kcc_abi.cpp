@@ -2922,3 +2922,128 @@ int kcc_drain(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu, const in
 }
 
 }  // extern "C"
+
+
+// ---- removal what-if: each candidate row's pods re-placed on the rest (kcc_consolidate.hip) ----
+
+namespace {
+
+struct ConsArgs {
+  kcc::FitNodes nd;  // the state is read only: nd's own pod_count / used_* pointers
+  const uint8_t* target;
+  kcc::DrainPods pods;
+  int64_t C;
+  const int64_t* cand;
+  kcc::ConsOut out;
+};
+
+// Argument checks of both entry points (host or device pointers alike).
+int check_consolidate(kcc_ctx* ctx, const ConsArgs& a) {
+  const kcc::FitNodes& nd = a.nd;
+  const int64_t P = a.pods.P;
+  if (nd.n < 0 || P < 0 || a.C < 0) return fail(ctx, KCC_EINVAL, "negative size");
+  if (nd.R < 0 || nd.R > KCC_EXT_MAX) return fail(ctx, KCC_EINVAL, "n_ext must be in [0, KCC_EXT_MAX]");
+  if (nd.n > kcc::GRP_MAX_NODES) return fail(ctx, KCC_EINVAL, "too many nodes (max 2^31 - 4096)");
+  if (P > kcc::DRAIN_MAX_PODS) return fail(ctx, KCC_EINVAL, "too many pods (max 2^31 - 4096)");
+  if (a.C > kcc::CONS_MAX_CAND) return fail(ctx, KCC_EINVAL, "too many candidates (max 2^31 - 4096)");
+  if (nd.n == 0 && P != 0) return fail(ctx, KCC_EINVAL, "pods without nodes");
+  const kcc::ConsOut& o = a.out;
+  if (a.C > 0 && (!a.cand || !o.evicted || !o.placed || !o.zero || !o.err))
+    return fail(ctx, KCC_EINVAL, "NULL candidate array");
+  if (nd.n > 0 && (!nd.alloc_cpu || !nd.alloc_mem || !nd.alloc_pods || !nd.pod_count ||
+                   !nd.used_cpu || !nd.used_mem || !a.pods.node_pod_ptr))
+    return fail(ctx, KCC_EINVAL, "NULL node array");
+  if (nd.R > 0 && nd.n > 0 && (!nd.alloc_x || !nd.used_x))
+    return fail(ctx, KCC_EINVAL, "NULL extra-resource array with n_ext > 0");
+  if (P > 0 && (!a.pods.pod_cpu || !a.pods.pod_mem)) return fail(ctx, KCC_EINVAL, "NULL pod array");
+  return KCC_OK;
+}
+
+// Device level: the checks, the degenerate cases and the launches on s.  No workspace.
+int consolidate_dev(kcc_ctx* ctx, const ConsArgs& a, hipStream_t s) {
+  const int rc = check_consolidate(ctx, a);
+  if (rc) return rc;
+  const kcc::ConsOut& o = a.out;
+  if (a.nd.n == 0 || a.C == 0) {  // nobody is evaluated: zeros, and every pod a non-candidate's
+    const size_t C = (size_t)a.C;
+    if (C) {
+      KCC_HIP(ctx, hipMemsetAsync(o.evicted, 0, 8 * C, s));
+      KCC_HIP(ctx, hipMemsetAsync(o.placed, 0, 8 * C, s));
+      KCC_HIP(ctx, hipMemsetAsync(o.zero, 0, 8 * C, s));
+      KCC_HIP(ctx, hipMemsetAsync(o.err, 0, 4 * C, s));
+    }
+    if (o.pod_target && a.pods.P > 0)
+      KCC_HIP(ctx, kcc::launch_fill_i64(a.pods.P, -2, o.pod_target, s));
+    return KCC_OK;
+  }
+  KCC_HIP(ctx, kcc::launch_consolidate(a.nd, a.target, a.pods, a.C, a.cand, o, s));
+  return KCC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kcc_consolidate_async(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* d_alloc_cpu,
+                          const int64_t* d_alloc_mem, const int64_t* d_alloc_pods, int64_t n_ext,
+                          const int64_t* d_alloc_x, const int64_t* d_pod_count,
+                          const uint64_t* d_used_cpu, const int64_t* d_used_mem,
+                          const int64_t* d_used_x, const uint8_t* d_target, int64_t n_pods,
+                          const int64_t* d_node_pod_ptr, const uint64_t* d_pod_cpu,
+                          const int64_t* d_pod_mem, const int64_t* d_pod_x,
+                          const uint8_t* d_pod_movable, int64_t n_cand, const int64_t* d_cand,
+                          int64_t* d_cand_evicted, int64_t* d_cand_placed, int64_t* d_cand_zero,
+                          int32_t* d_cand_err, int64_t* d_pod_target, void* stream) {
+  if (!ctx) return KCC_EINVAL;
+  const ConsArgs a{{n_nodes, d_alloc_cpu, d_alloc_mem, d_alloc_pods, d_pod_count, d_used_cpu,
+                    d_used_mem, n_ext, d_alloc_x, d_used_x, nullptr, 1},
+                   d_target,
+                   {n_pods, d_node_pod_ptr, d_pod_cpu, d_pod_mem, d_pod_x, d_pod_movable},
+                   n_cand, d_cand,
+                   {d_cand_evicted, d_cand_placed, d_cand_zero, d_cand_err, d_pod_target}};
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  return consolidate_dev(ctx, a, static_cast<hipStream_t>(stream));
+}
+
+int kcc_consolidate(kcc_ctx* ctx, int64_t n_nodes, const uint64_t* alloc_cpu,
+                    const int64_t* alloc_mem, const int64_t* alloc_pods, int64_t n_ext,
+                    const int64_t* alloc_x, const int64_t* pod_count, const uint64_t* used_cpu,
+                    const int64_t* used_mem, const int64_t* used_x, const uint8_t* target,
+                    int64_t n_pods, const int64_t* node_pod_ptr, const uint64_t* pod_cpu,
+                    const int64_t* pod_mem, const int64_t* pod_x, const uint8_t* pod_movable,
+                    int64_t n_cand, const int64_t* cand, int64_t* cand_evicted,
+                    int64_t* cand_placed, int64_t* cand_zero, int32_t* cand_err,
+                    int64_t* pod_target) {
+  if (!ctx) return KCC_EINVAL;
+  ConsArgs a{{n_nodes, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem, n_ext,
+              alloc_x, used_x, nullptr, 1},
+             target,
+             {n_pods, node_pod_ptr, pod_cpu, pod_mem, pod_x, pod_movable},
+             n_cand, cand,
+             {cand_evicted, cand_placed, cand_zero, cand_err, pod_target}};
+  int rc = check_consolidate(ctx, a);
+  if (rc) return rc;
+  // the host form reads the offsets: the CSR is well formed
+  if ((rc = check_csr(ctx, n_nodes, n_pods, node_pod_ptr))) return rc;
+  const int64_t n = n_nodes, P = n_pods, R = n_ext, C = n_cand;
+  Dev& dv = ctx->devs[0];
+  KCC_HIP(ctx, hipSetDevice(dv.device));
+  Stage st(ctx, dv);
+  kcc::FitNodes& nd = a.nd;
+  kcc::ConsOut& o = a.out;
+  if ((rc = st.in(nd.alloc_cpu, n)) || (rc = st.in(nd.alloc_mem, n)) ||
+      (rc = st.in(nd.alloc_pods, n)) || (rc = st.in(nd.alloc_x, R * n)) ||
+      (rc = st.in(nd.pod_count, n)) || (rc = st.in(nd.used_cpu, n)) ||
+      (rc = st.in(nd.used_mem, n)) || (rc = st.in(nd.used_x, R * n)) ||
+      (rc = st.in(a.target, n)) || (rc = st.in(a.pods.node_pod_ptr, csr_len(n))) ||
+      (rc = st.in(a.pods.pod_cpu, P)) || (rc = st.in(a.pods.pod_mem, P)) ||
+      (rc = st.in(a.pods.pod_x, R * P)) || (rc = st.in(a.pods.movable, P)) ||
+      (rc = st.in(a.cand, C)) || (rc = st.out(o.evicted, C)) || (rc = st.out(o.placed, C)) ||
+      (rc = st.out(o.zero, C)) || (rc = st.out(o.err, C)) || (rc = st.out(o.pod_target, P)) ||
+      (rc = consolidate_dev(ctx, a, dv.stream)))
+    return rc;
+  return st.finish();
+}
+
+}  // extern "C"

@@ -209,33 +209,13 @@ __global__ __launch_bounds__(DP_THREADS) void dp_rows_kernel(DpNodes nd, DpPlan 
         const uint64_t ac = nd.alloc_cpu[i], uc = nd.used_cpu[i];
         const int64_t am = nd.alloc_mem[i], um = nd.used_mem[i];
         const int64_t P = nd.alloc_pods[i], pc = nd.pod_count[i];
-        bool z = false;
-        int64_t qc = 0, qm = 0;
-        if (ac > uc) {  // CC:119-124 (uint64 compare and division, int() reinterprets)
-          if (c == 0) z = true;
-          else qc = (int64_t)((ac - uc) / c);
-        }
-        if (am > um) {  // CC:125-130 (int64, the difference wraps)
-          const int64_t fm = (int64_t)((uint64_t)am - (uint64_t)um);
-          if (m == 0) z = true;
-          else if (m == -1) qm = (int64_t)(0ull - (uint64_t)fm);  // MinInt64 / -1 == MinInt64
-          else qm = fm / m;
-        }
-        int64_t q = qc <= qm ? qc : qm;  // findMin, CC:133
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          if (x[r] != 0) {  // zero: not requested
-            const int64_t ax = nd.alloc_x[(int64_t)r * nd.n + i], ux = nd.used_x[(int64_t)r * nd.n + i];
-            int64_t qx = 0;
-            if (ax > ux) {
-              const int64_t fx = (int64_t)((uint64_t)ax - (uint64_t)ux);
-              qx = x[r] == -1 ? (int64_t)(0ull - (uint64_t)fx) : fx / x[r];
-            }
-            q = q <= qx ? q : qx;
-          }
-        }
-        if (q >= P) q = (int64_t)((uint64_t)P - (uint64_t)pc);  // CC:134-136, after all the mins
-        q = q < 0 ? 0 : q;                    // a negative clamp value holds nothing
+        bool z;
+        int64_t q = deploy_row_q<R>(ac, uc, am, um, P, pc, c, m, x,
+                                    [&](int r, int64_t& ax, int64_t& ux) {
+                                      ax = nd.alloc_x[(int64_t)r * nd.n + i];
+                                      ux = nd.used_x[(int64_t)r * nd.n + i];
+                                    },
+                                    z);
         q = (capk > 0 && q > capk) ? capk : q;  // the per-node cap: after the clamp
         q = q > Rk ? Rk : q;
         a = z ? 0u : (uint32_t)q;

@@ -982,6 +982,48 @@ inline bool deploy_sizes_ok(const FitNodes& nd, int64_t K) {
   return nd.n <= GRP_MAX_NODES && K <= DEPLOY_MAX_STEPS && nd.G <= GRP_MAX_CELLS &&
          nd.G * K <= GRP_MAX_CELLS;
 }
+#if defined(__HIPCC__)
+// What one row can take of one deploy step, before the per-node cap and the replica count:
+// kcc_fit_ext's q on the row's current state (64-bit integer arithmetic), the pod-slot clamp
+// after all the mins (CC:134-136), a negative value counted as 0.  z: the row would panic (a
+// zero cpu or memory request against free CPU or memory); the value returned is then not used.
+// load_x(r, ax, ux) fetches the row's allocatable and used amounts of extra resource r, and is
+// called for the requested resources alone.  The one copy of the step arithmetic: dp_rows
+// (kcc_deploy.hip) and the removal what-if's walk (kcc_consolidate.hip) both call it.
+template <int R, class LoadX>
+__device__ inline int64_t deploy_row_q(uint64_t ac, uint64_t uc, int64_t am, int64_t um, int64_t P,
+                                       int64_t pc, uint64_t c, int64_t m, const int64_t* x,
+                                       LoadX&& load_x, bool& z) {
+  z = false;
+  int64_t qc = 0, qm = 0;
+  if (ac > uc) {  // CC:119-124 (uint64 compare and division, int() reinterprets)
+    if (c == 0) z = true;
+    else qc = (int64_t)((ac - uc) / c);
+  }
+  if (am > um) {  // CC:125-130 (int64, the difference wraps)
+    const int64_t fm = (int64_t)((uint64_t)am - (uint64_t)um);
+    if (m == 0) z = true;
+    else if (m == -1) qm = (int64_t)(0ull - (uint64_t)fm);  // MinInt64 / -1 == MinInt64
+    else qm = fm / m;
+  }
+  int64_t q = qc <= qm ? qc : qm;  // findMin, CC:133
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (x[r] != 0) {  // zero: not requested
+      int64_t ax, ux;
+      load_x(r, ax, ux);
+      int64_t qx = 0;
+      if (ax > ux) {
+        const int64_t fx = (int64_t)((uint64_t)ax - (uint64_t)ux);
+        qx = x[r] == -1 ? (int64_t)(0ull - (uint64_t)fx) : fx / x[r];
+      }
+      q = q <= qx ? q : qx;
+    }
+  }
+  if (q >= P) q = (int64_t)((uint64_t)P - (uint64_t)pc);  // CC:134-136, after all the mins
+  return q < 0 ? 0 : q;                                   // a negative clamp value holds nothing
+}
+#endif
 // The plan's K steps on s, in order.  nd's pod_count / used_* are not read: the state arrays
 // are the four pointers after it, updated in place.  placed / nodes_used / step_err [K] are
 // written; placed_rows [K n] is nullable.  eligible [G K] uint8, nullable.
@@ -1048,6 +1090,27 @@ hipError_t launch_drain_plan(int64_t R, const DrainPods& pods, int64_t max_shape
 // dr_finish: the steps' outputs masked to j < D, and the summary.
 hipError_t launch_drain_finish(int64_t max_shapes, const DrainWork& w, const DrainOut& out,
                                hipStream_t s);
+
+// ---- removal what-if: each candidate row's pods re-placed on the rest (kcc_consolidate.hip,
+// DESIGN.md §4.16)
+constexpr int CONS_MAX_PODS = 1024;  // include/kcc.h KCC_CONS_MAX_PODS: a candidate's evicted pods
+constexpr int CONS_THREADS = 256;
+constexpr int CONS_IPT = 4;          // rows of a chunk per thread, CONS_THREADS apart
+constexpr int CONS_CHUNK = CONS_THREADS * CONS_IPT;  // 1024 (_lib.KCC_CONS_CHUNK restates it)
+constexpr int32_t CAND_OK = 0, CAND_BADROW = 1, CAND_TOOMANY = 2;  // include/kcc.h KCC_CAND_*
+constexpr int64_t CONS_MAX_CAND = ((int64_t)1 << 31) - 4096;       // one workgroup per candidate
+struct ConsOut {
+  int64_t* evicted;     // [C]
+  int64_t* placed;      // [C]
+  int64_t* zero;        // [C]
+  int32_t* err;         // [C]
+  int64_t* pod_target;  // [P], nullable
+};
+// pod_target (when given) filled with -2, then one workgroup per candidate.  nd.n, C >= 1; nd's
+// six state / allocatable arrays and alloc_x / used_x are read, nothing of them is written;
+// nd.group is not read.
+hipError_t launch_consolidate(const FitNodes& nd, const uint8_t* target, const DrainPods& pods,
+                              int64_t C, const int64_t* cand, const ConsOut& out, hipStream_t s);
 
 // ---- opt-in scheduler request model (kcc_pods.hip) ---------------
 hipError_t launch_pod_requests(int64_t n_pods, int64_t n_cont, int64_t n_init,

@@ -97,6 +97,29 @@ class DrainResult:
 
 
 @dataclass
+class ConsolidateResult:
+    """What CapacityEngine.consolidate returns, per candidate: the evicted pods, how many of
+    them were placed on the rest, how many request nothing (not tried) and the flag
+    (KCC_CAND_*); pod_target[p] = the row pod p went to, -1 not placed, -2 not evicted by any
+    candidate evaluated, -3 no requests (None unless asked for)."""
+    evicted: np.ndarray
+    placed: np.ndarray
+    zero: np.ndarray
+    err: np.ndarray
+    pod_target: np.ndarray | None
+
+    @property
+    def removable(self) -> np.ndarray:
+        """Strict: every evicted pod was placed."""
+        return (self.err == _lib.KCC_CAND_OK) & (self.placed == self.evicted)
+
+    @property
+    def removable_lenient(self) -> np.ndarray:
+        """Pods without requests count as placed: they fit anywhere."""
+        return (self.err == _lib.KCC_CAND_OK) & (self.placed + self.zero == self.evicted)
+
+
+@dataclass
 class ExplainResult:
     """What CapacityEngine.fit_explain returns: fit_capped's totals / err, the rows and the
     replicas of each cell by reason ([KCC_WHY_SLOTS, G, S]) and what stays free ([2 + R, G, S]);
@@ -624,6 +647,76 @@ class CapacityEngine:
             int(policy), int(max_shapes), _dp(summary), _dp(shape_cpu), _dp(shape_mem),
             _dp(shape_x), _dp(shape_count), _dp(shape_placed), _dp(shape_nodes), _dp(shape_err),
             _stream(stream)))
+
+    # -- removal what-if: each candidate row's pods re-placed on the rest (opt-in; DESIGN.md
+    # §4.16) ---------------------------------------------------------------------------------
+    def consolidate(self, alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu, used_mem, cand,
+                    node_pod_ptr, pod_cpu, pod_mem, alloc_x=None, used_x=None, pod_x=None,
+                    pod_movable=None, target=None, want_targets=True) -> "ConsolidateResult":
+        """For each row of `cand`, on its own: do the movable pods that run there (pods grouped
+        by node, node_pod_ptr [N + 1]; pod_movable None: all) fit on the other rows as they
+        stand (target None: every row may receive pods)?  Each pod goes to the first row in row
+        order that holds it, as a kcc_deploy step of one replica would place it; a candidate
+        sees only its own placements.  The state is read, never written."""
+        a = [_arr(x, t) for x, t in zip((alloc_cpu, alloc_mem, alloc_pods, pod_count, used_cpu,
+                                         used_mem),
+                                        (np.uint64, np.int64, np.int64, np.int64, np.uint64,
+                                         np.int64))]
+        n = a[0].size
+        if any(x.shape != (n,) for x in a):
+            raise ValueError("node arrays differ in length")
+        pc, pm = _arr(pod_cpu, np.uint64), _arr(pod_mem, np.int64)
+        P = pc.size
+        if pc.shape != (P,) or pm.shape != (P,):
+            raise ValueError("pod arrays differ in length")
+        ptr = _arr(node_pod_ptr, np.int64)
+        if n > 0 and ptr.shape != (n + 1,):
+            raise ValueError("node_pod_ptr must be [N + 1]")
+        ax = _arr(np.zeros((0, n)) if alloc_x is None else alloc_x, np.int64)
+        ux = _arr(np.zeros((0, n)) if used_x is None else used_x, np.int64)
+        if ax.ndim != 2 or ux.shape != ax.shape or ax.shape[1] != n:
+            raise ValueError("alloc_x and used_x must both be [R, N]")
+        R = ax.shape[0]
+        px = None if pod_x is None else _arr(pod_x, np.int64)
+        if px is not None and px.shape != (R, P):
+            raise ValueError("pod_x must be [R, P]")
+        mv = None if pod_movable is None else _arr(np.asarray(pod_movable) != 0, np.uint8)
+        if mv is not None and mv.shape != (P,):
+            raise ValueError("pod_movable must be [P]")
+        tg = None if target is None else _arr(np.asarray(target) != 0, np.uint8)
+        if tg is not None and tg.shape != (n,):
+            raise ValueError("target must be [N]")
+        cd = _arr(cand, np.int64)
+        if cd.ndim != 1:
+            raise ValueError("cand must be one-dimensional")
+        C_ = cd.size
+        ev, pl, ze = (np.zeros(C_, np.int64) for _ in range(3))
+        er = np.zeros(C_, np.int32)
+        tgt = np.zeros(P, np.int64) if want_targets else None
+        self._check(self._lib.kcc_consolidate(
+            self._h, n, _p(a[0]), _p(a[1]), _p(a[2]), R, _p(ax), _p(a[3]), _p(a[4]), _p(a[5]),
+            _p(ux), _p(tg), P, _p(ptr), _p(pc), _p(pm), _p(px), _p(mv), C_, _p(cd), _p(ev),
+            _p(pl), _p(ze), _p(er), _p(tgt)))
+        return ConsolidateResult(ev, pl, ze, er, tgt)
+
+    def consolidate_async(self, alloc_cpu, alloc_mem, alloc_pods, n_ext, alloc_x, pod_count,
+                          used_cpu, used_mem, used_x, target, node_pod_ptr, pod_cpu, pod_mem,
+                          pod_x, pod_movable, cand, cand_evicted, cand_placed, cand_zero,
+                          cand_err, pod_target, stream=None):
+        """Device form of consolidate (torch tensors on the engine's device): target and
+        pod_movable uint8 (or None), cand and the three counts int64 [C], cand_err int32 [C],
+        pod_target int64 [P] (or None).  Only enqueues on `stream`, the same launches whatever
+        the arrays hold: it can be captured into a graph.  The arguments go to the C-ABI as
+        they are (None: NULL), which validates them."""
+        n = 0 if alloc_cpu is None else alloc_cpu.numel()
+        p = 0 if pod_cpu is None else pod_cpu.numel()
+        c = 0 if cand is None else cand.numel()
+        self._check(self._lib.kcc_consolidate_async(
+            self._h, n, _dp(alloc_cpu), _dp(alloc_mem), _dp(alloc_pods), int(n_ext), _dp(alloc_x),
+            _dp(pod_count), _dp(used_cpu), _dp(used_mem), _dp(used_x), _dp(target), p,
+            _dp(node_pod_ptr), _dp(pod_cpu), _dp(pod_mem), _dp(pod_x), _dp(pod_movable), c,
+            _dp(cand), _dp(cand_evicted), _dp(cand_placed), _dp(cand_zero), _dp(cand_err),
+            _dp(pod_target), _stream(stream)))
 
     def capacity(self, node_ptr, cpu_req, mem_req, alloc_cpu, alloc_mem, alloc_pods, pod_count,
                  spec_cpu, spec_mem):
